@@ -2,7 +2,14 @@
 """Flagship benchmark: @parallel Llama-3-8B bf16 train step (BASELINE
 config 3) — tokens/sec, whole-job aggregate.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+                    [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON
+result line (ms_per_step = wall milliseconds per timed step). With
+--dump-outputs it first writes the last timed step's results as .npy
+files; seeds are fixed, so the same arguments give the same inputs on
+every run. --full is reserved for secondary measurements (none today).
 
 For N>1 the driver launches this under torch.distributed.run (one rank per
 GPU, RCCL over xGMI); this script is exactly the body the @parallel gang
@@ -60,7 +67,61 @@ def parse_args():
     p.add_argument("--tunableop", action="store_true",
                    help="enable PyTorch TunableOp (hipBLASLt algorithm "
                         "autotuning) during warmup")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step produced (loss, plus a fixed seeded sample "
+                        "of the updated parameters and of the gradients) "
+                        "as DIR/<name>.npy in float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check "
+                        "(none today: a plain run already does only "
+                        "what the headline figure needs — this is "
+                        "where any future extra belongs)")
     return p.parse_args()
+
+
+# elements sampled from each flat buffer by --dump-outputs (float32:
+# 8 MB per array, far below the 64 MB a dump may take in all)
+DUMP_SAMPLE = 1 << 21
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir, flat, step_losses):
+    """Write the last timed step's results as float32 .npy files.
+
+    loss.npy         [1]  loss returned by the last timed step
+    step_losses.npy  [K]  loss of every timed step, in order
+    params.npy       [n]  updated bf16 parameters (flat buffer sample)
+    grads.npy        [n]  gradients the optimizer consumed (same indices)
+
+    Buffers larger than DUMP_SAMPLE are sampled at indices drawn once
+    from a fixed seed, so two builds run with the same arguments dump
+    the same elements. Alignment padding between parameters is never
+    initialised and is left out.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    offsets = np.asarray(flat.offsets, dtype=np.int64)
+    numels = np.asarray([p.numel() for p in flat.params], dtype=np.int64)
+    if flat.total <= DUMP_SAMPLE:
+        idx = np.arange(flat.total, dtype=np.int64)
+    else:
+        rng = np.random.RandomState(DUMP_SEED)
+        idx = np.sort(rng.randint(0, flat.total, size=DUMP_SAMPLE,
+                                  dtype=np.int64))
+    owner = np.searchsorted(offsets, idx, side="right") - 1
+    idx = idx[idx - offsets[owner] < numels[owner]]  # drop padding
+    sel = torch.from_numpy(idx).to(flat.flat_param.device)
+    arrays = {
+        "loss": step_losses[-1:].float(),
+        "step_losses": step_losses.float(),
+        "params": flat.flat_param.index_select(0, sel).float(),
+        "grads": flat.flat_grad.index_select(0, sel).float(),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.detach().cpu().numpy().astype(np.float32))
 
 
 def main():
@@ -260,6 +321,9 @@ def main():
                     / max(1, len(comm_ms) - args.warmup), 2),
             },
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, flat, torch.stack(
+                [l.detach().reshape(()) for l in losses[args.warmup:]]))
         print(json.dumps(out), flush=True)
 
     if distributed:
