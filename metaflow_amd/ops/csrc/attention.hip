@@ -1,108 +1,414 @@
-// Shared MFMA-16x16 helpers + attention backward delta preprocess for
-// gfx950 (bf16, D=128). The flash fwd/bwd kernels themselves live in
-// attention_v2.hip (8-wave 32x32 swapped-QK^T structure); unaligned
-// seqlens are zero-padded to the 256 boundary by the Python wrapper
-// (exact for causal attention — end-padded keys are causally masked for
-// every real query row).
+// Flash attention train kernels for gfx950 (bf16, head dim 128, GQA):
+//   attn_fwd_v2_kernel        forward, writes O and lse
+//   attn_bwd_delta_kernel     delta = rowsum(dO * O)
+//   attn_bwd_dkdv_v2_kernel   dK/dV fp32 partials, one query head per block
+//   dkdv_reduce_kernel        sums the G partials per kv head -> bf16
+//   attn_bwd_dq_v2_kernel     dQ
+// The three MFMA kernels share one structure: 512 threads = 8 waves x 32
+// rows, mfma_f32_32x32x16_bf16, and the SWAPPED product S^T = K·Q^T (or
+// S = Q·K^T in dkdv) so that each lane's C-register column is its OWN row
+// of the wave's operand held in registers. Consequences:
+//  * softmax statistics are per-lane scalars: the online softmax is a
+//    serial max/sum over the lane's 16 C registers per 32-row sub-tile
+//    plus one shfl_xor(32) — no cross-lane group reductions, no LDS
+//    round-trip for P;
+//  * P / dS become the A operand of the second GEMM in-register
+//    (col_to_afrags: packed bf16 pairs + one shfl_xor(32) exchange);
+//  * LDS holds only the streamed operand tiles, in the 16-wide PANEL
+//    layout below, which serves contiguous A-fragment reads and
+//    hardware-transposed B-fragment reads from the same copy.
 //
-// MFMA fragment layout (guide §3, measured m89/m91):
-//   C/D: col = lane&15, row = (lane>>4)*4 + reg
-//   A (MxK): lane holds A[lane&15][(lane>>4)*8 + i], i = 0..7
-//   B (KxN): lane holds B[(lane>>4)*8 + i][lane&15]
-// so every A read wants M-major storage [m][k] and every B read wants
-// N-major storage [n][k]; tiles are staged in the layout each operand needs.
+// MFMA 32x32x16 layouts (probed on HW by dbg_mfma32_kernel; the panel /
+// transposed-read / col_to_afrags chain by dbg_attn_layout_kernel):
+//  A (32x16): lane holds A[lane&31][(lane>>5)*8 + i]
+//  B (16x32): lane holds B[(lane>>5)*8 + i][lane&31]
+//  C (32x32): col = lane&31, row = c_row(reg, lane>>5)
+//
+// Shapes: q/o/dout [B,H,S,128], k/v [B,Hkv,S,128], lse/delta [B,H,S] fp32,
+// S % 256 == 0 (the Python wrapper zero-pads unaligned causal seqlens:
+// end-padded keys are causally masked for every real query row).
 
 #include "common.h"
 
 #define ATT_D 128
 
-typedef __attribute__((ext_vector_type(4))) float f4;
+typedef __attribute__((ext_vector_type(16))) float f16f;
 
-DEV f4 mfma16(bf16x8 a, bf16x8 b, f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+DEV f16f mfma32(bf16x8 a, bf16x8 b, f16f c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// byte offset of element (r, c) in a swizzled LDS tile with ROWB bytes/row
-// (rowb must be a power of 2; the XOR is masked so it stays inside the row
-// — rowb=64 tiles get a 4-row spread instead of 8, still conflict-free
-// enough at 2 lanes/bank)
-DEV int swz(int r, int c, int rowb) {
-  // spread up to 16 rows across 16-byte slots (256B rows get the full
-  // 16-way spread -> 2 lanes/slot for 32-row reads; narrower rows are
-  // masked down automatically)
-  return r * rowb + (((c) * 2) ^ (((r & 15) << 4) & (rowb - 1)));
+// wave / lane coordinates every kernel here uses: lane = 32*hi + l32.
+// (dq and dkdv compute the same four values inline: taking them from
+// here changed how the compiler narrows their epilogue address math.)
+struct WaveCoord {
+  int wid, lane, l32, hi;
+};
+
+DEV WaveCoord wave_coord() {
+  WaveCoord c;
+  c.wid = threadIdx.x / WAVE;
+  c.lane = threadIdx.x & (WAVE - 1);
+  c.l32 = c.lane & 31;
+  c.hi = c.lane >> 5;
+  return c;
 }
 
-// load an 8-element fragment from a swizzled tile row (c must be mult of 8)
-DEV bf16x8 frag8(const short* tile, int r, int c, int rowb) {
-  return *(const bf16x8*)((const char*)tile + swz(r, c, rowb));
+// row of the 32x32 C tile held in register r of a lane in half-wave hi
+DEV int c_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// pack two fp32 into one u32 of two bf16 (lo, hi): single
+// v_cvt_pk_bf16_f32 on gfx950 (RNE) — the manual shift/round sequence
+// was ~12 VALU ops and the P->A-fragment repack runs twice per subtile
+// in every attention kernel
+DEV unsigned int pack_bf2(float lo, float hi) {
+  union { __hip_bfloat162 h; unsigned int u; } c;
+  c.h = __float22bfloat162_rn(make_float2(lo, hi));
+  return c.u;
 }
 
-// 16-lane-group reductions: rows of the C layout live in lanes with equal
-// lane>>4; reduce across the 16 lanes of each group.
-DEV float group_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 1, WAVE));
-  v = fmaxf(v, __shfl_xor(v, 2, WAVE));
-  v = fmaxf(v, __shfl_xor(v, 4, WAVE));
-  v = fmaxf(v, __shfl_xor(v, 8, WAVE));
-  return v;
+// Turn a per-lane C-tile column (st[NT][16]: lane holds X[row][mycol] for
+// rows c_row(r, hi) of NT 32-row sub-tiles) into MFMA A-fragments with
+// m = mycol and k = the row dimension: pack bf16 pairs, exchange with the
+// partner half-wave (shfl_xor 32), assemble 2*NT k-steps of 16 rows.
+template <int NT>
+DEV void col_to_afrags(const f16f* st, bf16x8* pa, int hi) {
+  unsigned int pk[NT * 8], xp[NT * 8];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int j2 = 0; j2 < 8; ++j2)
+      pk[t * 8 + j2] = pack_bf2(st[t][j2 * 2], st[t][j2 * 2 + 1]);
+#pragma unroll
+  for (int i = 0; i < NT * 8; ++i) xp[i] = __shfl_xor(pk[i], 32, WAVE);
+#pragma unroll
+  for (int ks = 0; ks < NT * 2; ++ks) {
+    union {
+      unsigned int w[4];
+      bf16x8 v;
+    } u;
+    if (hi == 0) {
+      u.w[0] = pk[4 * ks];
+      u.w[1] = pk[4 * ks + 1];
+      u.w[2] = xp[4 * ks];
+      u.w[3] = xp[4 * ks + 1];
+    } else {
+      u.w[0] = xp[4 * ks + 2];
+      u.w[1] = xp[4 * ks + 3];
+      u.w[2] = pk[4 * ks + 2];
+      u.w[3] = pk[4 * ks + 3];
+    }
+    pa[ks] = u.v;
+  }
 }
 
-DEV float group_sum(float v) {
-  v += __shfl_xor(v, 1, WAVE);
-  v += __shfl_xor(v, 2, WAVE);
-  v += __shfl_xor(v, 4, WAVE);
-  v += __shfl_xor(v, 8, WAVE);
-  return v;
-}
+// ================= panel layout + hardware transpose reads =================
+// A [ROWS][128] bf16 tile stored as 8 panels of [ROWS][16]: element
+// (row, d) lives at (d>>4)*ROWS*16 + row*16 + (d&15). Properties:
+//  * staging from row-major global is pure vec8 -> vec8 (no scalar scatter);
+//  * A-fragment reads (row fixed per lane, 8 contiguous d) are one
+//    16-byte read: panel (d0>>4), offset row*16 + (d0&8);
+//  * B-fragments with K = the row dimension come from ds_read_b64_tr_b16
+//    (tr_load_bfrags) — no transposed copy of the tile is ever made.
 
-// stage a [ROWS][128] bf16 tile from global (row-major) into swizzled LDS
 template <int ROWS, int BLOCK>
-DEV void stage_rm(short* dst, const short* src, long long src_row_stride) {
-  constexpr int VPR = ATT_D / 8;  // vec8 per row
-  constexpr int TOT = ROWS * VPR;
+DEV void stage_panel(short* dst, const short* src,
+                     long long src_row_stride) {
+  constexpr int TOT = ROWS * 16;  // vec8 slots
 #pragma unroll
   for (int it = 0; it < (TOT + BLOCK - 1) / BLOCK; ++it) {
-    int idx = it * BLOCK + threadIdx.x;
+    const int idx = it * BLOCK + threadIdx.x;
     if (idx < TOT) {
-      int r = idx / VPR, c8 = idx % VPR;
+      const int r = idx % ROWS, c8 = idx / ROWS;
       bf16x8 v = *(const bf16x8*)(src + r * src_row_stride + c8 * 8);
-      *(bf16x8*)((char*)dst + swz(r, c8 * 8, ATT_D * 2)) = v;
+      *(bf16x8*)(dst + (c8 >> 1) * (ROWS * 16) + r * 16 + (c8 & 1) * 8) =
+          v;
     }
   }
 }
 
-// stage a [ROWS][128] global tile TRANSPOSED into a [128][ROWS] swizzled
-// LDS tile (ROWS = 32 or 64; rowb = ROWS*2 bytes)
-template <int ROWS, int BLOCK>
-DEV void stage_tr(short* dst, const short* src, long long src_row_stride) {
-  constexpr int VPR = ATT_D / 8;
-  constexpr int TOT = ROWS * VPR;
+template <int ROWS>
+DEV bf16x8 frag8_panel(const short* tile, int row, int d0) {
+  return *(const bf16x8*)(tile + (d0 >> 4) * (ROWS * 16) + row * 16
+                          + (d0 & 15));
+}
+
+// issue one tr-read: returns 2 VGPRs holding rows (base_q .. base_q+3) at
+// this lane's column; caller must s_waitcnt lgkmcnt + sched_barrier before
+// consuming (inline-asm DS reads are invisible to the compiler's waitcnt
+// insertion).
+DEV unsigned long long tr_read(const short* lds_ptr) {
+  // generic pointers to __shared__ carry the LDS offset in the low 32
+  // bits; ds_* instructions take that 32-bit address
+  unsigned int addr = (unsigned int)(unsigned long long)lds_ptr;
+  unsigned long long out;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(out) : "v"(addr));
+  return out;
+}
+
+union BFrag {
+  unsigned long long u[2];
+  bf16x8 v;
+};
+
+// Issue the 8 transposed reads that give this lane its four B-fragments
+// (n = 0..3: d columns n*32 + l32) for the 16 tile rows row0 .. row0+15
+// of a [ROWS][128] panel tile; K = the row dimension. Waiting is the
+// CALLER's job (s_waitcnt lgkmcnt + sched_barrier before the MFMAs), so
+// callers can pipeline several groups with counted waits.
+//
+// ds_read_b64_tr_b16 semantics: each lane loads 64b at its OWN address;
+// the HW transposes 16-bit elements within each 16-lane group (a [4][16]
+// tile): elem = base + (l&15) + j*16 + (l>>4)*64 walks column (l&15) of
+// that subtile, which in panel storage is exactly 4 consecutive rows at
+// one d-column. To make lane l = 32*hi + l32 RECEIVE rows row0+hi*8+j at
+// column n*32+l32, lane l must LOAD the 4 elements of row
+// row0+hi*8+((l>>2)&3) at col offset 4*(l&3) of panel 2n + ((l>>4)&1);
+// the second read covers rows +4..+7.
+template <int ROWS>
+DEV void tr_load_bfrags(BFrag bfr[4], const short* tile, int row0,
+                        int lane, int hi) {
+  const int tr_lane_off = (((lane >> 2) & 3) * 16) + (lane & 3) * 4;
+  const int tr_panel = ((lane >> 4) & 1) * (ROWS * 16);
 #pragma unroll
-  for (int it = 0; it < (TOT + BLOCK - 1) / BLOCK; ++it) {
-    int idx = it * BLOCK + threadIdx.x;
-    if (idx < TOT) {
-      int r = idx / VPR, c8 = idx % VPR;
-      bf16x8 v = *(const bf16x8*)(src + r * src_row_stride + c8 * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        *(short*)((char*)dst + swz(c8 * 8 + j, r, ROWS * 2)) = v[j];
-    }
+  for (int n = 0; n < 4; ++n) {
+    const int base = n * 2 * (ROWS * 16) + tr_panel
+                     + (row0 + hi * 8) * 16 + tr_lane_off;
+    bfr[n].u[0] = tr_read(tile + base);
+    bfr[n].u[1] = tr_read(tile + base + 4 * 16);
   }
 }
 
-// intra-wave LDS exchange fence: the P/dS round-trips move data between
-// lanes of the SAME wave; DS ops issue in order per wave, so a full block
-// barrier is overkill — we only need the writes drained and the compiler
-// forbidden from reordering the reads above the writes (per-lane alias
-// analysis would otherwise allow it).
-DEV void wave_lds_fence() {
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_wave_barrier();
+// ---- accumulator-tile epilogue ----
+DEV void put_elem(short* p, float x) { *p = f2bf(x); }
+DEV void put_elem(float* p, float x) { *p = x; }
+
+// Store a wave's 32 x 128 accumulator tile (acc[n]: C tile of d columns
+// n*32..n*32+31) to rows row0.. of a row-major [rows][128] array starting
+// at dst[off0]. With ROW_SCALE, row i is first multiplied by the value of
+// `lane_scale` held by the lane whose l32 == i (the swapped structure
+// keeps per-row scalars in the lane that owns the row). Used by the
+// forward and the layout probe; dq and dkdv store the same way but keep
+// the loop open-coded, because routing them through here changed their
+// register allocation (dq 252 -> 254 VGPRs; dkdv sits at the 256 limit).
+// Likewise tr_load_bfrags above serves dq and the probe; the forward and
+// dkdv keep open-coded copies of the same addressing.
+template <bool ROW_SCALE, typename T>
+DEV void store_acc_tile(T* dst, long long off0, int row0, const f16f acc[4],
+                        int l32, int hi, float lane_scale = 1.f) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row_local = c_row(r, hi);
+    float f = 1.f;
+    if (ROW_SCALE) f = __shfl(lane_scale, row_local + 32 * hi, WAVE);
+    const long long obase = off0 + (long long)(row0 + row_local) * ATT_D;
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+      put_elem(dst + obase + n * 32 + l32,
+               ROW_SCALE ? acc[n][r] * f : acc[n][r]);
+  }
+}
+
+// ============================ FORWARD ======================================
+// Grid (S/256, H, B), 8 waves x 32 q rows; each lane keeps its own q row
+// in registers (8 x bf16x8) and streams 64-row K/V tiles through LDS.
+// LDS: K and V panel tiles, double-buffered = 2 x 2 x 16 KiB = 64 KiB.
+
+template <int BLOCK>  // BLOCK = 512 (8 waves)
+__global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
+    const short* __restrict__ q, const short* __restrict__ k,
+    const short* __restrict__ v, short* __restrict__ o,
+    float* __restrict__ lse, int B, int H, int Hkv, int S, float scale,
+    int causal) {
+  constexpr int BQ = 256, BKV = 64;  // 8 waves x 32 q rows
+  // double-buffered K/V tiles in the 16-wide PANEL layout [8][64][16]:
+  // staging is pure vec8 writes, K A-fragments are contiguous panel
+  // reads, V B-fragments come from ds_read_b64_tr_b16 (no transposed
+  // copy). Stage j+1 overlaps compute on j (async-stage split).
+  __shared__ short kp[2][BKV * ATT_D];
+  __shared__ short vp[2][BKV * ATT_D];
+
+  const int qb = blockIdx.x;
+  const int h = blockIdx.y;
+  const int b = blockIdx.z;
+  const int hk = h / (H / Hkv);
+  const WaveCoord c = wave_coord();
+  const int wid = c.wid, lane = c.lane, l32 = c.l32, hi = c.hi;
+
+  const int my_qrow = qb * BQ + wid * 32 + l32;  // this lane's q row
+  const long long hoff = ((long long)b * H + h) * S;
+  const long long qoff = (hoff + qb * BQ) * ATT_D;
+  const long long kvoff0 = ((long long)b * Hkv + hk) * S * ATT_D;
+
+  // Q row in registers: q_reg[s] = Q[my_qrow][s*16 + hi*8 .. +8]
+  bf16x8 q_reg[8];
+  {
+    const short* qrow = q + (hoff + my_qrow) * ATT_D;
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+      q_reg[s] = *(const bf16x8*)(qrow + s * 16 + hi * 8);
+  }
+
+  float m_run = -INFINITY;
+  float l_run = 0.f;
+  f16f acc_o[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) acc_o[n] = (f16f){};
+
+  // per-thread staging slices: 2 x bf16x8 of K and of V per tile
+  const int tid = threadIdx.x;
+  bf16x8 stg_k[2], stg_v[2];
+  int stg_r[2], stg_c8[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int idx = u * BLOCK + tid;
+    stg_r[u] = idx / 16;
+    stg_c8[u] = idx % 16;
+  }
+
+  // global loads and LDS writes of a tile are split so the loads for
+  // tile j+1 are in flight during the MFMAs on tile j; kept as macros
+  // because they close over the staging registers above
+#define MFX_STAGE_LOAD(jj)                                               \
+  {                                                                      \
+    const short* kb_ = k + kvoff0 + (long long)(jj) * BKV * ATT_D;       \
+    const short* vb_ = v + kvoff0 + (long long)(jj) * BKV * ATT_D;       \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                      \
+      stg_k[u] = *(const bf16x8*)(kb_ + stg_r[u] * ATT_D + stg_c8[u] * 8);\
+      stg_v[u] = *(const bf16x8*)(vb_ + stg_r[u] * ATT_D + stg_c8[u] * 8);\
+    }                                                                    \
+  }
+
+#define MFX_STAGE_WRITE(buf)                                             \
+  {                                                                      \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                      \
+      const int pel_ = (stg_c8[u] >> 1) * (BKV * 16) + stg_r[u] * 16     \
+                       + (stg_c8[u] & 1) * 8;                            \
+      *(bf16x8*)(kp[buf] + pel_) = stg_k[u];                             \
+      *(bf16x8*)(vp[buf] + pel_) = stg_v[u];                             \
+    }                                                                    \
+  }
+
+  const int kv_tiles =
+      causal ? (qb * BQ + BQ) / BKV : S / BKV;  // causal bound incl diag
+  MFX_STAGE_LOAD(0);
+  MFX_STAGE_WRITE(0);
+  __syncthreads();
+  for (int j = 0; j < kv_tiles; ++j) {
+    const int cur = j & 1;
+    if (j + 1 < kv_tiles) MFX_STAGE_LOAD(j + 1);  // issue loads early
+
+    // wave-uniform skip: this wave's rows are all below the tile's kv
+    // range (fully masked) — staging + barrier still run below
+    const bool active = !causal || (j * BKV <= qb * BQ + wid * 32 + 31);
+    if (active) {
+
+    // ---- S^T = K (64x128) @ Q^T: two 32-kv sub-tiles ----
+    f16f st[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      st[t] = (f16f){};
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        bf16x8 kf = frag8_panel<BKV>(kp[cur], t * 32 + l32,
+                                     s * 16 + hi * 8);
+        st[t] = mfma32(kf, q_reg[s], st[t]);
+      }
+    }
+
+    // ---- scale + causal mask + in-register online softmax ----
+    // lane's value (t, r) is S[my_qrow][kv = j*64 + t*32 + c_row(r,hi)]
+    const bool diag = causal && (j * BKV + BKV > qb * BQ);
+    float pmax = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float sv = st[t][r] * scale;
+        if (diag) {
+          const int kvg = j * BKV + t * 32 + c_row(r, hi);
+          if (kvg > my_qrow) sv = -INFINITY;
+        }
+        st[t][r] = sv;
+        pmax = fmaxf(pmax, sv);
+      }
+    }
+    pmax = fmaxf(pmax, __shfl_xor(pmax, 32, WAVE));
+    const float newm = fmaxf(m_run, pmax);
+    const float rescale = __expf(m_run - newm);
+    m_run = newm;
+
+    float psum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float e = __expf(st[t][r] - newm);
+        st[t][r] = e;
+        psum += e;
+      }
+    psum += __shfl_xor(psum, 32, WAVE);
+    l_run = l_run * rescale + psum;
+
+    // ---- rescale O: the factor for local row c_row(r, hi) is held by
+    // the lanes with l32 == that row; broadcast via shfl ----
+    {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float f = __shfl(rescale, c_row(r, hi) + 32 * hi, WAVE);
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc_o[n][r] *= f;
+      }
+    }
+
+    // ---- P -> bf16 A-fragments via packed pairs + partner exchange ----
+    bf16x8 pa[4];
+    col_to_afrags<2>(st, pa, hi);
+
+    // ---- PV: O(32q x 128d) += P(32q x 64kv) @ V(64kv x 128d) ----
+    // B-fragments via hardware transpose: same addressing as
+    // tr_load_bfrags<BKV> (derivation there), open-coded because the
+    // helper form measured 0.6% slower here (3.24 vs 3.22 ms at
+    // B=8 H=32 S=4096) with an identical main loop
+    {
+      const int tr_lane_off = (((lane >> 2) & 3) * 16) + (lane & 3) * 4;
+      const int tr_panel = ((lane >> 4) & 1) * (BKV * 16);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        BFrag bfr[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+          const int base = n * 2 * (BKV * 16) + tr_panel
+                           + (ks * 16 + hi * 8) * 16 + tr_lane_off;
+          bfr[n].u[0] = tr_read(vp[cur] + base);
+          bfr[n].u[1] = tr_read(vp[cur] + base + 4 * 16);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)");
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+          acc_o[n] = mfma32(pa[ks], bfr[n].v, acc_o[n]);
+      }
+    }
+    }  // active
+
+    if (j + 1 < kv_tiles) MFX_STAGE_WRITE(cur ^ 1);
+    __syncthreads();
+  }
+#undef MFX_STAGE_LOAD
+#undef MFX_STAGE_WRITE
+
+  // ---- epilogue: O /= l (row-matched), write bf16 + lse ----
+  float inv_l = 1.f / l_run;
+  store_acc_tile<true>(o, qoff, wid * 32, acc_o, l32, hi, inv_l);
+  if (hi == 0)
+    lse[hoff + my_qrow] = m_run + __logf(l_run);
 }
 
 // ===================== BACKWARD: delta preprocess ==========================
 // delta[row] = rowsum(dO[row] * O[row]); one wave per row, 2 elems/lane.
+// A separate tiny kernel so both MFMA backward kernels stay
+// elementwise-free.
 __global__ void attn_bwd_delta_kernel(const short* __restrict__ dout,
                                       const short* __restrict__ o,
                                       float* __restrict__ delta,
@@ -117,4 +423,338 @@ __global__ void attn_bwd_delta_kernel(const short* __restrict__ dout,
             + bf2f(dr[lane + 64]) * bf2f(orow[lane + 64]);
   s = wave_sum(s);
   if (lane == 0) delta[row] = s;
+}
+
+// ===================== BACKWARD: dQ ========================================
+// Grid (S/256, H, B), 8 waves x 32 q rows. Swapped structure: lane's
+// C-column is its OWN q row, so lse/delta are per-lane scalars and
+// dS^T -> dS A-fragments use the same col_to_afrags dance. Q and dO rows
+// live in registers. LDS: one K and one V panel tile (2 x 16 KiB =
+// 32 KiB); the K tile serves both S^T (A-fragments) and dS·K
+// (transposed B-fragments).
+
+template <int BLOCK>
+__global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
+    const short* __restrict__ q, const short* __restrict__ k,
+    const short* __restrict__ v, const short* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    short* __restrict__ dq, int B, int H, int Hkv, int S, float scale,
+    int causal) {
+  constexpr int BQ = 256, BKV = 64;
+  __shared__ short kp[BKV * ATT_D];    // K panels
+  __shared__ short vp[BKV * ATT_D];    // V panels
+
+  const int qb = blockIdx.x;
+  const int h = blockIdx.y;
+  const int b = blockIdx.z;
+  const int hk = h / (H / Hkv);
+  const int wid = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int l32 = lane & 31;
+  const int hi = lane >> 5;
+
+  const int my_qrow = qb * BQ + wid * 32 + l32;
+  const long long hoff = ((long long)b * H + h) * S;
+  const long long qoff = (hoff + qb * BQ) * ATT_D;
+  const long long kvoff0 = ((long long)b * Hkv + hk) * S * ATT_D;
+
+  bf16x8 q_reg[8], do_reg[8];
+  {
+    const short* qrow = q + (hoff + my_qrow) * ATT_D;
+    const short* drow = dout + (hoff + my_qrow) * ATT_D;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      q_reg[s] = *(const bf16x8*)(qrow + s * 16 + hi * 8);
+      do_reg[s] = *(const bf16x8*)(drow + s * 16 + hi * 8);
+    }
+  }
+  const float my_lse = lse[hoff + my_qrow];
+  const float my_del = delta[hoff + my_qrow];
+
+  f16f acc_dq[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) acc_dq[n] = (f16f){};
+
+  const int kv_tiles = causal ? (qb * BQ + BQ) / BKV : S / BKV;
+  for (int j = 0; j < kv_tiles; ++j) {
+    __syncthreads();
+    stage_panel<BKV, BLOCK>(kp, k + kvoff0 + (long long)j * BKV * ATT_D,
+                            ATT_D);
+    stage_panel<BKV, BLOCK>(vp, v + kvoff0 + (long long)j * BKV * ATT_D,
+                            ATT_D);
+    __syncthreads();
+    if (causal && j * BKV > qb * BQ + wid * 32 + 31) continue;
+
+    // per 32-kv sub-tile: S^T, dP^T, dS, dQ — keeps live regs low
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f16f st = (f16f){}, dpt = (f16f){};
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        bf16x8 kf = frag8_panel<BKV>(kp, t * 32 + l32, s * 16 + hi * 8);
+        bf16x8 vf = frag8_panel<BKV>(vp, t * 32 + l32, s * 16 + hi * 8);
+        st = mfma32(kf, q_reg[s], st);
+        dpt = mfma32(vf, do_reg[s], dpt);
+      }
+      // dS = P * (dP - delta) * scale, P = exp(S*scale - lse), causal
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kvg = j * BKV + t * 32 + c_row(r, hi);
+        float p = 0.f;
+        if (!causal || kvg <= my_qrow)
+          p = __expf(st[r] * scale - my_lse);
+        st[r] = p * (dpt[r] - my_del) * scale;
+      }
+      // dQ(32q x 128d) += dS(32q x 32kv) @ K(32kv x 128d)
+      bf16x8 pa[2];
+      col_to_afrags<1>(&st, pa, hi);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        BFrag bfr[4];
+        tr_load_bfrags<BKV>(bfr, kp, t * 32 + ks * 16, lane, hi);
+        asm volatile("s_waitcnt lgkmcnt(0)");
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+          acc_dq[n] = mfma32(pa[ks], bfr[n].v, acc_dq[n]);
+      }
+    }
+  }
+
+  // epilogue: C row = q local, col = d. Open-coded, with the row formula
+  // written out: store_acc_tile moves this kernel from 252 to 254 VGPRs,
+  // and c_row() here keeps the compiler from narrowing the row offset
+  // to 32 bits (25 more instructions, measurably slower).
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row_local = (r & 3) + 8 * (r >> 2) + 4 * hi;
+    const long long obase =
+        qoff + (long long)(wid * 32 + row_local) * ATT_D;
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+      dq[obase + n * 32 + l32] = f2bf(acc_dq[n][r]);
+  }
+}
+
+// ===================== BACKWARD: dK/dV =====================================
+// Grid (S/256, H, B) — one Q-HEAD per block, mirroring the dq kernel's
+// structure (which measures 2.2x more TF/s than the round-1 dkdv that
+// looped all G q-heads inside a (S/256, Hkv, B) grid: 4x fewer blocks
+// with a skewed causal trapezoid starved/imbalanced the chip). Each
+// block accumulates its head's (dK, dV) contribution in registers and
+// writes FP32 PARTIALS laid out [B, H, S, D]; dkdv_reduce_kernel sums
+// the G partials per kv head and converts to bf16 — numerically
+// identical to the old in-register fp32 accumulation across g. 8 waves
+// x 32 kv rows; K/V rows stay register-resident (the compiler hoists
+// them at the 256-VGPR budget, 0 spill — guarded by
+// tests/test_attn_kernel_resources.py). LDS: Q and dO panel tiles
+// (2 x 16 KiB) + 64 lse + 64 delta floats = 33280 bytes.
+//
+// This kernel sits EXACTLY at the register limit, and its code generation
+// is fragile: taking the coordinates from wave_coord(), the transposed
+// reads from tr_load_bfrags or the epilogue from store_acc_tile each
+// changed its SGPR count, its compiler-placed waits or its epilogue
+// length. It therefore keeps those three pieces open-coded; they must
+// stay in step with the helpers above.
+
+template <int BLOCK>
+__global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
+    const short* __restrict__ q, const short* __restrict__ k,
+    const short* __restrict__ v, const short* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    float* __restrict__ dk_part, float* __restrict__ dv_part,
+    int B, int H, int Hkv, int S, float scale, int causal) {
+  constexpr int BKVB = 256, BQ2 = 64;
+  __shared__ short qp[BQ2 * ATT_D];    // Q panels
+  __shared__ short dop[BQ2 * ATT_D];   // dO panels
+  __shared__ float lse_s[BQ2];
+  __shared__ float del_s[BQ2];
+
+  const int kvb = blockIdx.x;
+  const int h = blockIdx.y;           // q head
+  const int b = blockIdx.z;
+  const int G = H / Hkv;
+  const int hk = h / G;               // kv head this block feeds
+  const int wid = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int l32 = lane & 31;
+  const int hi = lane >> 5;
+
+  const int my_kvrow = kvb * BKVB + wid * 32 + l32;
+  const long long kvoff =
+      (((long long)b * Hkv + hk) * S + kvb * BKVB) * ATT_D;
+
+  // K/V rows for this wave's 32 kv rows; register-resident across the
+  // whole q loop at the 256-VGPR budget
+  const short* krow = k + kvoff + (long long)(wid * 32 + l32) * ATT_D;
+  const short* vrow = v + kvoff + (long long)(wid * 32 + l32) * ATT_D;
+
+  f16f acc_dk[4], acc_dv[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    acc_dk[n] = (f16f){};
+    acc_dv[n] = (f16f){};
+  }
+
+  const long long hoff = ((long long)b * H + h) * S;
+  const int jq0 = causal ? (kvb * BKVB) / BQ2 : 0;
+  const int nq = S / BQ2;
+  for (int jq = jq0; jq < nq; ++jq) {
+    __syncthreads();
+    const short* qsrc = q + (hoff + (long long)jq * BQ2) * ATT_D;
+    const short* dsrc = dout + (hoff + (long long)jq * BQ2) * ATT_D;
+    stage_panel<BQ2, BLOCK>(qp, qsrc, ATT_D);
+    stage_panel<BQ2, BLOCK>(dop, dsrc, ATT_D);
+    if (threadIdx.x < BQ2) {
+      lse_s[threadIdx.x] = lse[hoff + jq * BQ2 + threadIdx.x];
+      del_s[threadIdx.x] = delta[hoff + jq * BQ2 + threadIdx.x];
+    }
+    __syncthreads();
+    // wave-uniform skip: all of this wave's kv rows above every q row
+    if (causal && jq * BQ2 + BQ2 - 1 < kvb * BKVB + wid * 32) continue;
+
+    // per 32-q sub-tile: S, dP, P/dS, dV, dK — keeps live regs low
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f16f st = (f16f){}, dpt = (f16f){};
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        bf16x8 qf = frag8_panel<BQ2>(qp, t * 32 + l32, s * 16 + hi * 8);
+        bf16x8 df = frag8_panel<BQ2>(dop, t * 32 + l32, s * 16 + hi * 8);
+        bf16x8 kr = *(const bf16x8*)(krow + s * 16 + hi * 8);
+        bf16x8 vr = *(const bf16x8*)(vrow + s * 16 + hi * 8);
+        st = mfma32(qf, kr, st);
+        dpt = mfma32(df, vr, dpt);
+      }
+      // P (into st) with causal mask q >= kv; dS (into dpt). lse/delta
+      // come as f32x4 GROUP loads: the per-element lse_s[qrl] reads were
+      // 64 scalar ds_read_b32 per tile (the dq kernel holds its lse in
+      // a register) — the disassembly showed them, plus their waitcnts,
+      // matching the mfma count, which is where dkdv's efficiency gap
+      // vs dq was hiding. qrl = t*32 + c_row(r, hi), so r = g*4+j walks
+      // 4 consecutive floats at t*32 + 8g + 4hi.
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int q0l = t * 32 + g * 8 + 4 * hi;
+        const f32x4 lv = *(const f32x4*)&lse_s[q0l];
+        const f32x4 dl = *(const f32x4*)&del_s[q0l];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = g * 4 + j;
+          const int qrg = jq * BQ2 + q0l + j;
+          float p = 0.f;
+          if (!causal || qrg >= my_kvrow)
+            p = __expf(st[r] * scale - lv[j]);
+          st[r] = p;
+          dpt[r] = p * (dpt[r] - dl[j]) * scale;
+        }
+      }
+      // dV(32kv x 128d) += P^T(32kv x 32q) @ dO(32q x 128d), then
+      // dK += dS^T @ Q — FOUR transposed-read groups, software-pipelined
+      // with COUNTED waits: group g+1's 8 DS reads issue before waiting
+      // on group g (DS returns in order, so lgkmcnt(8) = "the earlier 8
+      // are done"), so the transpose-read latency of every group but
+      // the last hides under the previous group's MFMAs. A counter run
+      // showed both backward kernels stalled on these full-stop groups,
+      // not on LDS bandwidth (LdsUtil 12%, conflicts 4%).
+      bf16x8 pa[2], pak[2];
+      col_to_afrags<1>(&st, pa, hi);
+      BFrag bfr[2][4];
+      // same addressing as tr_load_bfrags<BQ2> (derivation there)
+      const int tr_lane_off = (((lane >> 2) & 3) * 16) + (lane & 3) * 4;
+      const int tr_panel = ((lane >> 4) & 1) * (BQ2 * 16);
+      const short* g_tile[4] = {dop, dop, qp, qp};
+      int g_q0[4];
+      g_q0[0] = t * 32;
+      g_q0[1] = t * 32 + 16;
+      g_q0[2] = t * 32;
+      g_q0[3] = t * 32 + 16;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int base = n * 2 * (BQ2 * 16) + tr_panel
+                         + (g_q0[0] + hi * 8) * 16 + tr_lane_off;
+        bfr[0][n].u[0] = tr_read(g_tile[0] + base);
+        bfr[0][n].u[1] = tr_read(g_tile[0] + base + 4 * 16);
+      }
+      col_to_afrags<1>(&dpt, pak, hi);  // VALU under the first DS group
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cur = g & 1;
+        if (g < 3) {
+#pragma unroll
+          for (int n = 0; n < 4; ++n) {
+            const int base = n * 2 * (BQ2 * 16) + tr_panel
+                             + (g_q0[g + 1] + hi * 8) * 16 + tr_lane_off;
+            bfr[cur ^ 1][n].u[0] = tr_read(g_tile[g + 1] + base);
+            bfr[cur ^ 1][n].u[1] = tr_read(g_tile[g + 1] + base + 4 * 16);
+          }
+          asm volatile("s_waitcnt lgkmcnt(8)");
+        } else {
+          asm volatile("s_waitcnt lgkmcnt(0)");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const bf16x8 a = (g < 2) ? pa[g] : pak[g - 2];
+        f16f* acc = (g < 2) ? acc_dv : acc_dk;
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+          acc[n] = mfma32(a, bfr[cur][n].v, acc[n]);
+      }
+    }
+  }
+
+  // epilogue: fp32 partials at [b, h, kv row, d]; row formula written
+  // out for the same reason as in dq
+  const long long poff = (hoff + (long long)kvb * BKVB) * ATT_D;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row_local = (r & 3) + 8 * (r >> 2) + 4 * hi;
+    const long long obase =
+        poff + (long long)(wid * 32 + row_local) * ATT_D;
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      dk_part[obase + n * 32 + l32] = acc_dk[n][r];
+      dv_part[obase + n * 32 + l32] = acc_dv[n][r];
+    }
+  }
+}
+
+// Sum the G per-q-head fp32 partials into the kv head's bf16 (dK, dV).
+// Memory-bound; vectorized f32x4 loads, grid-stride.
+__global__ void dkdv_reduce_kernel(const float* __restrict__ dk_part,
+                                   const float* __restrict__ dv_part,
+                                   short* __restrict__ dk,
+                                   short* __restrict__ dv,
+                                   long long n4_kv, int G,
+                                   long long head_elems) {
+  // n4_kv = B*Hkv*S*D/4. Flat kv vec4-index i4 -> kv slot (b*Hkv + hk);
+  // its G partials live at heads slot*G + g of the [B, H, S, D] buffer
+  // (h = hk*G + g).
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i4 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i4 < n4_kv; i4 += stride) {
+    const long long i = i4 * 4;
+    const long long slot = i / head_elems;
+    const long long rem = i - slot * head_elems;
+    const float* kp = dk_part + slot * G * head_elems + rem;
+    const float* vp = dv_part + slot * G * head_elems + rem;
+    f32x4 ks = *(const f32x4*)kp;
+    f32x4 vs = *(const f32x4*)vp;
+    for (int g = 1; g < G; ++g) {
+      const f32x4 k2 = *(const f32x4*)(kp + (long long)g * head_elems);
+      const f32x4 v2 = *(const f32x4*)(vp + (long long)g * head_elems);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        ks[j] += k2[j];
+        vs[j] += v2[j];
+      }
+    }
+    bf16x4 ko, vo;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ko[j] = f2bf(ks[j]);
+      vo[j] = f2bf(vs[j]);
+    }
+    *(bf16x4*)(dk + i) = ko;
+    *(bf16x4*)(dv + i) = vo;
+  }
 }

@@ -11,7 +11,6 @@
 #include "adam.hip"
 #include "cross_entropy.hip"
 #include "attention.hip"
-#include "attention_v2.hip"
 #include "decode.hip"
 #include "debug_kernels.hip"
 
@@ -270,14 +269,14 @@ void adamw(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v,
         bfm(p), bf(g), m.data_ptr<float>(), v.data_ptr<float>(), master_ptr,
         n, (float)lr, (float)beta1, (float)beta2, (float)eps,
         (float)weight_decay, bias_c1, bias_c2, (float)grad_scale);
-  HIP_CHECK_KERNEL();
+    HIP_CHECK_KERNEL();
   } else {
     adamw_f32_kernel<<<grid_for(n), kBlock, 0, cur_stream()>>>(
         p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
         v.data_ptr<float>(), n, (float)lr, (float)beta1, (float)beta2,
         (float)eps, (float)weight_decay, bias_c1, bias_c2,
         (float)grad_scale);
-  HIP_CHECK_KERNEL();
+    HIP_CHECK_KERNEL();
   }
 }
 
@@ -343,56 +342,47 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor o,
                                     torch::Tensor dout, torch::Tensor lse,
                                     double scale, bool causal) {
-  const int B = q.size(0), H = q.size(1), S = q.size(2);
+  check_bf16(q, "q");
+  check_bf16(k, "k");
+  check_bf16(v, "v");
+  check_bf16(o, "o");
+  check_bf16(dout, "dout");
+  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const int Hkv = k.size(1);
+  TORCH_CHECK(D == 128, "attention requires head dim 128");
+  TORCH_CHECK(S % 256 == 0, "attention kernel requires seqlen % 256 == 0");
+  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat32 &&
+                  lse.is_contiguous(),
+              "lse must be contiguous fp32 on GPU");
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H &&
+                  lse.size(2) == S,
+              "lse must have shape [B,H,S]");
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
-  auto delta = torch::empty({B, H, S}, q.options().dtype(torch::kFloat32));
-
-  const long long rows = (long long)B * H * S;
-  {
-    int rows_per_block = kBlock / 64;
-    long long blocks = (rows + rows_per_block - 1) / rows_per_block;
-    attn_bwd_delta_kernel<<<(int)blocks, kBlock, 0, cur_stream()>>>(
-        bf(dout), bf(o), delta.data_ptr<float>(), rows);
-  HIP_CHECK_KERNEL();
-  }
-  TORCH_CHECK(S % 256 == 0, "attention kernel requires seqlen % 256 == 0");
-  // dkdv: one q-head per block into fp32 partials [B,H,S,D], then a
-  // memory-bound reduction over the G partials per kv head (see
-  // attention_v2.hip rationale — 4x the workgroups of the per-kv-head
-  // grid and balanced causal trapezoids)
   auto f32opts = q.options().dtype(torch::kFloat32);
+  auto delta = torch::empty({B, H, S}, f32opts);
+  // dkdv writes one fp32 partial per q head, [B,H,S,D]; the reduction
+  // sums the G partials per kv head (rationale in attention.hip)
   auto dk_part = torch::empty({B, H, S, 128}, f32opts);
   auto dv_part = torch::empty({B, H, S, 128}, f32opts);
-  dim3 gkv(S / 256, H, B);
-  // MFX_ATTN_DKDV_SPLIT=1: dV-only + dK-only kernels (64 live
-  // accumulator VGPRs each instead of 128; S^T recomputed) — the
-  // register-pressure/ILP experiment documented in attention_v2.hip
-  static const bool split_dkdv = [] {
-    const char* e = getenv("MFX_ATTN_DKDV_SPLIT");
-    return e && e[0] == '1';
-  }();
-  if (split_dkdv) {
-    attn_bwd_dv_v2_kernel<512><<<gkv, 512, 0, cur_stream()>>>(
-        bf(q), bf(k), bf(dout), lse.data_ptr<float>(),
-        dv_part.data_ptr<float>(), B, H, Hkv, S, (float)scale,
-        causal ? 1 : 0);
-    HIP_CHECK_KERNEL();
-    attn_bwd_dk_v2_kernel<512><<<gkv, 512, 0, cur_stream()>>>(
-        bf(q), bf(k), bf(v), bf(dout), lse.data_ptr<float>(),
-        delta.data_ptr<float>(), dk_part.data_ptr<float>(), B, H, Hkv,
-        S, (float)scale, causal ? 1 : 0);
-    HIP_CHECK_KERNEL();
-  } else {
-    attn_bwd_dkdv_v2_kernel<512><<<gkv, 512, 0, cur_stream()>>>(
-        bf(q), bf(k), bf(v), bf(dout), lse.data_ptr<float>(),
-        delta.data_ptr<float>(), dk_part.data_ptr<float>(),
-        dv_part.data_ptr<float>(), B, H, Hkv, S, (float)scale,
-        causal ? 1 : 0);
+  const int icausal = causal ? 1 : 0;
+  const dim3 grid(S / 256, H, B);
+
+  {
+    const long long rows = (long long)B * H * S;
+    const int rows_per_block = kBlock / 64;
+    const long long blocks = (rows + rows_per_block - 1) / rows_per_block;
+    attn_bwd_delta_kernel<<<(int)blocks, kBlock, 0, cur_stream()>>>(
+        bf(dout), bf(o), delta.data_ptr<float>(), rows);
     HIP_CHECK_KERNEL();
   }
+  attn_bwd_dkdv_v2_kernel<512><<<grid, 512, 0, cur_stream()>>>(
+      bf(q), bf(k), bf(v), bf(dout), lse.data_ptr<float>(),
+      delta.data_ptr<float>(), dk_part.data_ptr<float>(),
+      dv_part.data_ptr<float>(), B, H, Hkv, S, (float)scale, icausal);
+  HIP_CHECK_KERNEL();
   {
     const long long n4_kv = (long long)B * Hkv * S * 128 / 4;
     const long long head_elems = (long long)S * 128;
@@ -403,11 +393,10 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
         bfm(dv), n4_kv, H / Hkv, head_elems);
     HIP_CHECK_KERNEL();
   }
-  dim3 gq(S / 256, H, B);
-  attn_bwd_dq_v2_kernel<512><<<gq, 512, 0, cur_stream()>>>(
+  attn_bwd_dq_v2_kernel<512><<<grid, 512, 0, cur_stream()>>>(
       bf(q), bf(k), bf(v), bf(dout), lse.data_ptr<float>(),
       delta.data_ptr<float>(), bfm(dq), B, H, Hkv, S, (float)scale,
-      causal ? 1 : 0);
+      icausal);
   HIP_CHECK_KERNEL();
   return {dq, dk, dv};
 }
@@ -456,29 +445,7 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc,
   return attn_decode_varlen(q, kc, vc, lengths, L, scale);
 }
 
-}  // namespace
-
-
-namespace {
-torch::Tensor dbg_st(torch::Tensor kmat, torch::Tensor qmat) {
-  auto out = torch::empty({64, 32},
-                          kmat.options().dtype(torch::kFloat32));
-  dbg_st_kernel<<<1, 256, 0, cur_stream()>>>(bf(kmat), bf(qmat),
-                                             out.data_ptr<float>());
-  HIP_CHECK_KERNEL();
-  return out;
-}
-torch::Tensor dbg_dv(torch::Tensor pmat, torch::Tensor bmat) {
-  auto out = torch::empty({64, 128},
-                          pmat.options().dtype(torch::kFloat32));
-  dbg_dv_kernel<<<1, 256, 0, cur_stream()>>>(bf(pmat), bf(bmat),
-                                             out.data_ptr<float>());
-  HIP_CHECK_KERNEL();
-  return out;
-}
-}  // namespace
-
-namespace {
+// ------------------------------------------------------- layout probes
 torch::Tensor dbg_mfma32(torch::Tensor a, torch::Tensor b) {
   auto out = torch::empty({32, 32}, a.options().dtype(torch::kFloat32));
   dbg_mfma32_kernel<<<1, 64, 0, cur_stream()>>>(bf(a), bf(b),
@@ -486,6 +453,24 @@ torch::Tensor dbg_mfma32(torch::Tensor a, torch::Tensor b) {
   HIP_CHECK_KERNEL();
   return out;
 }
+
+std::vector<torch::Tensor> dbg_attn_layout(torch::Tensor t,
+                                           torch::Tensor x) {
+  check_bf16(t, "t");
+  check_bf16(x, "x");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == 64 && t.size(1) == 128,
+              "t must be [64,128]");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == 32 && x.size(1) == 128,
+              "x must be [32,128]");
+  auto f32opts = t.options().dtype(torch::kFloat32);
+  auto st = torch::empty({64, 32}, f32opts);
+  auto out = torch::empty({32, 128}, f32opts);
+  dbg_attn_layout_kernel<<<1, 64, 0, cur_stream()>>>(
+      bf(t), bf(x), st.data_ptr<float>(), out.data_ptr<float>());
+  HIP_CHECK_KERNEL();
+  return {st, out};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -519,7 +504,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_varlen", &attn_decode_varlen,
         "flash-decode with per-sequence cache lengths (int32 [B]; "
         "length 0 = inactive slot, output 0)");
-  m.def("dbg_st", &dbg_st, "debug S^T path");
-  m.def("dbg_dv", &dbg_dv, "debug dV path");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
+  m.def("dbg_attn_layout", &dbg_attn_layout,
+        "attention panel / transposed-read / col_to_afrags layout probe");
 }

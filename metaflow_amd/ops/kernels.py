@@ -321,15 +321,36 @@ def _attn_pad_len(S, causal):
     return (S + _ATTN_ALIGN - 1) // _ATTN_ALIGN * _ATTN_ALIGN
 
 
+def _attn_fwd_padded(q, k, v, scale, causal):
+    """Pad to the kernel tile and run the forward kernel.
+
+    Returns the PADDED (q, k, v, o, lse) — what backward needs — and the
+    padded seqlen; callers slice o / lse back to the real length.
+    """
+    Sp = _attn_pad_len(q.size(2), causal)
+    qp, kp, vp = _pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp)
+    o, lse = hip_ext().attn_fwd(qp, kp, vp, scale, causal)
+    return qp, kp, vp, o, lse, Sp
+
+
+def _attn_bwd_padded(qp, kp, vp, op, dout, lse_p, scale, causal, S):
+    """Run the backward kernels on padded (q, k, v, o, lse) and an
+    unpadded dout; returns (dq, dk, dv) sliced back to S rows. Padded
+    dout rows are zero, so ds == 0 there."""
+    Sp = qp.size(2)
+    grads = hip_ext().attn_bwd(qp, kp, vp, op, _pad_seq(dout, Sp), lse_p,
+                               scale, causal)
+    if Sp != S:
+        grads = [g[:, :, :S].contiguous() for g in grads]
+    return tuple(grads)
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, causal):
         S = q.size(2)
-        Sp = _attn_pad_len(S, causal)
-        qp = _pad_seq(q, Sp)
-        kp = _pad_seq(k, Sp)
-        vp = _pad_seq(v, Sp)
-        o, lse = hip_ext().attn_fwd(qp, kp, vp, scale, causal)
+        qp, kp, vp, o, lse, Sp = _attn_fwd_padded(q, k, v, scale, causal)
+        # backward gets the kernel's own padded lse
         ctx.save_for_backward(qp, kp, vp, o, lse)
         ctx.scale = scale
         ctx.causal = causal
@@ -339,14 +360,8 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         q, k, v, o, lse = ctx.saved_tensors
-        S, Sp = ctx.real_s, q.size(2)
-        dp = _pad_seq(dout, Sp)
-        dq, dk, dv = hip_ext().attn_bwd(q, k, v, o, dp, lse,
-                                        ctx.scale, ctx.causal)
-        if Sp != S:
-            dq = dq[:, :, :S].contiguous()
-            dk = dk[:, :, :S].contiguous()
-            dv = dv[:, :, :S].contiguous()
+        dq, dk, dv = _attn_bwd_padded(q, k, v, o, dout, lse, ctx.scale,
+                                      ctx.causal, ctx.real_s)
         return dq, dk, dv, None, None
 
 
@@ -392,9 +407,7 @@ def attn_fwd_raw(q, k, v, scale, causal=True):
     """
     if q.is_cuda:
         S = q.size(2)
-        Sp = _attn_pad_len(S, causal)
-        o, lse = hip_ext().attn_fwd(_pad_seq(q, Sp), _pad_seq(k, Sp),
-                                    _pad_seq(v, Sp), scale, causal)
+        _, _, _, o, lse, Sp = _attn_fwd_padded(q, k, v, scale, causal)
         if Sp != S:
             o = o[:, :, :S].contiguous()
             lse = lse[:, :, :S].contiguous()
@@ -414,27 +427,24 @@ def attn_bwd_raw(q, k, v, o, dout, lse, scale, causal=True):
     per-chunk backward a ring-attention pass needs: p is formed from the
     global lse and delta from the global o, so each chunk's (dq, dk, dv)
     contribution sums to the true gradient. Mirrors the HIP kernels'
-    formula (attention_v2.hip: p = exp(s*scale - lse),
+    formula (attention.hip: p = exp(s*scale - lse),
     ds = p * (dp - delta) * scale).
     """
     if q.is_cuda:
         S = q.size(2)
         Sp = _attn_pad_len(S, causal)
         if Sp == S:
-            return hip_ext().attn_bwd(q.contiguous(), k.contiguous(),
-                                      v.contiguous(), o.contiguous(),
-                                      dout.contiguous(), lse, scale, causal)
-        # padded rows: dout rows are zero so ds == 0 there; padded lse
-        # rows must be finite for exp() — zero q/k gives lse=log(n), but
-        # here lse came from the CALLER (global ring statistic) so pad
-        # with zeros explicitly (p = exp(0-0) is finite, ds still 0).
-        lse_p = lse.new_zeros((lse.size(0), lse.size(1), Sp))
-        lse_p[:, :, :S] = lse
-        dq, dk, dv = hip_ext().attn_bwd(
-            _pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp),
-            _pad_seq(o, Sp), _pad_seq(dout, Sp), lse_p, scale, causal)
-        return (dq[:, :, :S].contiguous(), dk[:, :, :S].contiguous(),
-                dv[:, :, :S].contiguous())
+            lse_p = lse.contiguous()
+        else:
+            # padded lse rows must be finite for exp(); lse comes from
+            # the CALLER here (a global ring statistic), so pad it with
+            # zeros explicitly (p = exp(0-0) is finite, ds is still 0
+            # because the padded dout rows are zero)
+            lse_p = lse.new_zeros((lse.size(0), lse.size(1), Sp))
+            lse_p[:, :, :S] = lse
+        return _attn_bwd_padded(_pad_seq(q, Sp), _pad_seq(k, Sp),
+                                _pad_seq(v, Sp), _pad_seq(o, Sp), dout,
+                                lse_p, scale, causal, S)
     G = q.size(1) // k.size(1)
     Hkv = k.size(1)
     s = _ref_scores(q, k, scale, causal)
@@ -484,13 +494,11 @@ def attn_decode_varlen(q, k_cache, v_cache, lengths, scale,
     the call hipGraph-capturable (no host read of lengths — the kernel
     chunks from the device lengths, empty splits cost nothing).
     """
-    import torch as _torch
-
     if q.is_cuda:
-        if not _torch.is_tensor(lengths):
-            lengths = _torch.tensor(lengths, dtype=_torch.int32,
-                                    device=q.device)
-        lengths = lengths.to(device=q.device, dtype=_torch.int32)
+        if not torch.is_tensor(lengths):
+            lengths = torch.tensor(lengths, dtype=torch.int32,
+                                   device=q.device)
+        lengths = lengths.to(device=q.device, dtype=torch.int32)
         if max_len is None:
             max_len = int(lengths.max().item())
         return hip_ext().attn_decode_varlen(
@@ -499,12 +507,12 @@ def attn_decode_varlen(q, k_cache, v_cache, lengths, scale,
     for b in range(q.size(0)):
         n = int(lengths[b])
         if n == 0:
-            outs.append(_torch.zeros_like(q[b:b + 1]))
+            outs.append(torch.zeros_like(q[b:b + 1]))
             continue
         outs.append(attention_ref(q[b:b + 1], k_cache[b:b + 1, :, :n],
                                   v_cache[b:b + 1, :, :n], scale,
                                   causal=False))
-    return _torch.cat(outs, 0)
+    return torch.cat(outs, 0)
 
 
 # ================================ adam =====================================
@@ -536,11 +544,9 @@ def decode_tokens_u16(raw):
     copy moves 2 B/token instead of 8; CPU: numpy view). The data-pipe
     decode for pretraining shards (SURVEY §2.4 foreach data path).
     """
-    import torch as _torch
-
     if raw.is_cuda:
         return hip_ext().decode_tokens_u16(raw.contiguous())
-    return raw.view(_torch.int16).to(_torch.int64) & 0xFFFF
+    return raw.view(torch.int16).to(torch.int64) & 0xFFFF
 
 
 def add_bf16(a, b):

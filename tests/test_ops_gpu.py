@@ -149,12 +149,17 @@ def test_attention_fwd(dev, B, H, Hkv, S):
     assert rel_err(o, o_ref) < 2e-2, "fwd mismatch"
 
 
-@pytest.mark.parametrize("S", [256, 257, 100])
-def test_attention_bwd(dev, S):
+@pytest.mark.parametrize("B,H,Hkv,S", [
+    pytest.param(1, 4, 2, 256, id="256"),
+    pytest.param(1, 4, 2, 257, id="257"),
+    pytest.param(1, 4, 2, 100, id="100"),
+    # B>1 and G=4 partial-slot indexing, two kv blocks x several q tiles
+    pytest.param(2, 8, 2, 512, id="b2-g4-512"),
+])
+def test_attention_bwd(dev, B, H, Hkv, S):
     from metaflow_amd.ops import kernels as K
 
     torch.manual_seed(0)
-    B, H, Hkv = 1, 4, 2
     q = torch.randn(B, H, S, 128, dtype=torch.bfloat16, device=dev,
                     requires_grad=True)
     k = torch.randn(B, Hkv, S, 128, dtype=torch.bfloat16, device=dev,
@@ -201,7 +206,7 @@ def test_rope_qkv_fused(dev):
 
 
 def test_attention_noncausal(dev):
-    """Non-causal kernel path (causal=0 in attention_v2.hip) — the
+    """Non-causal kernel path (causal=0 in attention.hip) — the
     off-diagonal chunk op of ring attention (parallel/ring_attention.py):
     fwd o + lse and all three grads vs the fp32 reference."""
     import math
@@ -334,6 +339,26 @@ def test_mfma32_layout_probe(dev):
     c = ext.dbg_mfma32(a, b)
     ref = a.float() @ b.float()
     assert rel_err(c, ref) < 1e-3
+
+
+def test_attn_layout_probe(dev):
+    """Isolation guard for the attention kernels' layout chain, run through
+    the production helpers: panel staging, panel A-fragments, the
+    C-column -> A-fragment repack and the hardware-transposed B-fragment
+    reads. Inputs from {-1, 0, 1}: x·t^T holds integers of magnitude
+    <= 128 (exact in bf16) and the second product integers <= 8192 (exact
+    in fp32), so both outputs must EQUAL the fp32 matmul; x and t are
+    independent, so a transposed or permuted layout cannot pass."""
+    from metaflow_amd.ops import kernels as K
+
+    ext = K.hip_ext()
+    g = torch.Generator().manual_seed(7)
+    tf = torch.randint(-1, 2, (64, 128), generator=g).float()
+    xf = torch.randint(-1, 2, (32, 128), generator=g).float()
+    st, out = ext.dbg_attn_layout(tf.to(dev, torch.bfloat16),
+                                  xf.to(dev, torch.bfloat16))
+    assert torch.equal(st.cpu(), tf @ xf.T)
+    assert torch.equal(out.cpu(), (xf @ tf.T) @ tf)
 
 
 def test_add_rmsnorm_fused(dev):
