@@ -139,9 +139,10 @@ class DecoderLayer(nn.Module):
                 o = K.attn_decode(q, kc, vc, pos + 1,
                                   1.0 / math.sqrt(hd))
             else:
-                o = _attn_with_cache(q, kc[:, :, :pos + S],
-                                     vc[:, :, :pos + S],
-                                     1.0 / math.sqrt(hd), pos)
+                # S new rows at pos > 0 (speculative verify block, later
+                # prefill chunks): append kernel over the whole cache
+                # allocation (append.hip)
+                o = K.attn_append(q, kc, vc, pos, 1.0 / math.sqrt(hd))
         elif cp_group is not None:
             from ..parallel.ring_attention import ring_attention
 
@@ -217,23 +218,12 @@ class KVCache(object):
 
 
 def _attn_with_cache(q, k_all, v_all, scale, pos):
-    """Attention of the s new queries (global positions pos..pos+s)
-    against all T cached kv positions: full visibility of the prefix,
-    causal within the new block. Plain torch ops (fp32 softmax) — decode
-    blocks are tiny, the flash kernels handle the big prefill."""
-    B, H, s, D = q.shape
-    Hkv = k_all.size(1)
-    T = k_all.size(2)
-    G = H // Hkv
-    kf = k_all.float().repeat_interleave(G, dim=1)
-    vf = v_all.float().repeat_interleave(G, dim=1)
-    att = torch.matmul(q.float(), kf.transpose(-1, -2)) * scale
-    kv_pos = torch.arange(T, device=q.device)
-    q_pos = pos + torch.arange(s, device=q.device)
-    mask = kv_pos[None, :] <= q_pos[:, None]          # [s, T]
-    att = att.masked_fill(~mask, float("-inf"))
-    p = torch.softmax(att, dim=-1)
-    return torch.matmul(p, vf).to(q.dtype)
+    """Eager fp32 reference for the s new queries (global positions
+    pos..pos+s-1) against the T = pos+s cached rows in k_all/v_all.
+    Kept as an alias of K.attn_append_ref for callers and tests that
+    pass pre-sliced caches; no model path uses it — cached forwards go
+    through K.attn_append (HIP kernel on GPU, this formula on CPU)."""
+    return K.attn_append_ref(q, k_all, v_all, pos, scale)
 
 
 class LlamaForCausalLM(nn.Module):

@@ -268,8 +268,6 @@ class MixtralDecoderLayer(nn.Module):
         v = self.v_proj(y).view(B, S, cfg.num_kv_heads,
                                 cfg.head_dim).transpose(1, 2)
         if cache is not None:
-            from .llama import _attn_with_cache
-
             kc, vc, pos = cache.k[layer_idx], cache.v[layer_idx], cache.pos
             kc[:, :, pos:pos + S] = kk
             vc[:, :, pos:pos + S] = v
@@ -284,10 +282,10 @@ class MixtralDecoderLayer(nn.Module):
             else:
                 import math
 
-                o = _attn_with_cache(q.contiguous(),
-                                     kc[:, :, :pos + S],
-                                     vc[:, :, :pos + S],
-                                     1.0 / math.sqrt(cfg.head_dim), pos)
+                # S new rows at pos > 0: append kernel over the whole
+                # cache allocation (append.hip)
+                o = K.attn_append(q.contiguous(), kc, vc, pos,
+                                  1.0 / math.sqrt(cfg.head_dim))
         else:
             o = K.attention(q, kk, v)
         o = o.transpose(1, 2).reshape(B, S, cfg.num_heads * cfg.head_dim)

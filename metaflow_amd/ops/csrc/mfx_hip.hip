@@ -11,6 +11,7 @@
 #include "adam.hip"
 #include "cross_entropy.hip"
 #include "attention.hip"
+#include "append.hip"
 #include "decode.hip"
 #include "debug_kernels.hip"
 
@@ -445,6 +446,69 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc,
   return attn_decode_varlen(q, kc, vc, lengths, L, scale);
 }
 
+// ------------------------------------------------------ append attention
+// Sq new query rows per sequence at device-side offsets pos[b], against
+// the cache rows 0 .. pos[b]+Sq-1 (append.hip). max_len bounds
+// max(pos) + Sq and only sizes the split count: pos is never read here.
+torch::Tensor attn_append(torch::Tensor q, torch::Tensor kc,
+                          torch::Tensor vc, torch::Tensor pos,
+                          long max_len, double scale) {
+  check_bf16(q, "q");
+  check_bf16(kc, "kc");
+  check_bf16(vc, "vc");
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128 && q.size(2) >= 1,
+              "append expects q [B,H,Sq,128]");
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2);
+  TORCH_CHECK(kc.dim() == 4 && kc.size(0) == B && kc.size(3) == 128,
+              "append expects k_cache [B,Hkv,Lmax,128]");
+  TORCH_CHECK(vc.sizes() == kc.sizes(),
+              "k_cache and v_cache must have the same shape");
+  const int Hkv = kc.size(1), Lmax = kc.size(2);
+  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  TORCH_CHECK(max_len >= 1 && max_len <= Lmax,
+              "max_len must be in [1, Lmax]");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
+              pos.numel() == B && pos.is_contiguous(),
+              "pos must be int32 [B] on GPU");
+  // one wave (32 query rows) for the verify block, four for a chunk
+  const bool small = Sq <= 32;
+  const int bq = small ? 32 : 128;
+  const int q_tiles = (Sq + bq - 1) / bq;
+  // enough workgroups to fill 256 CUs, chunks of >= ~256 cache rows
+  const long wgs = (long)B * H * q_tiles;
+  int splits = (int)std::max<long>(1, (small ? 1024 : 512) / wgs);
+  splits = (int)std::min<long>(splits, (max_len + 255) / 256);
+  splits = std::max(splits, 1);
+  auto o = torch::empty_like(q);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  torch::Tensor o_part, ml_part;
+  float* o_part_p = nullptr;
+  float* ml_part_p = nullptr;
+  if (splits > 1) {
+    o_part = torch::empty({splits, B, H, Sq, 128}, f32);
+    ml_part = torch::empty({splits, B, H, Sq, 2}, f32);
+    o_part_p = o_part.data_ptr<float>();
+    ml_part_p = ml_part.data_ptr<float>();
+  }
+  dim3 grid(q_tiles * splits, H, B);
+  if (small)
+    attn_append_kernel<1><<<grid, 64, 0, cur_stream()>>>(
+        bf(q), bf(kc), bf(vc), pos.data_ptr<int>(), bfm(o), o_part_p,
+        ml_part_p, B, H, Hkv, Sq, Lmax, splits, (float)scale);
+  else
+    attn_append_kernel<4><<<grid, 256, 0, cur_stream()>>>(
+        bf(q), bf(kc), bf(vc), pos.data_ptr<int>(), bfm(o), o_part_p,
+        ml_part_p, B, H, Hkv, Sq, Lmax, splits, (float)scale);
+  HIP_CHECK_KERNEL();
+  if (splits > 1) {
+    const long long R = (long long)B * H * Sq;
+    attn_append_merge_kernel<<<(int)((R + 3) / 4), 256, 0, cur_stream()>>>(
+        o_part_p, ml_part_p, bfm(o), R, splits);
+    HIP_CHECK_KERNEL();
+  }
+  return o;
+}
+
 // ------------------------------------------------------- layout probes
 torch::Tensor dbg_mfma32(torch::Tensor a, torch::Tensor b) {
   auto out = torch::empty({32, 32}, a.options().dtype(torch::kFloat32));
@@ -504,6 +568,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_varlen", &attn_decode_varlen,
         "flash-decode with per-sequence cache lengths (int32 [B]; "
         "length 0 = inactive slot, output 0)");
+  m.def("attn_append", &attn_append,
+        "append attention: Sq query rows at per-sequence offsets pos "
+        "(int32 [B]) over the KV cache (q [B,H,Sq,128])");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");

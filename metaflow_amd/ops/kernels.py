@@ -515,6 +515,89 @@ def attn_decode_varlen(q, k_cache, v_cache, lengths, scale,
     return torch.cat(outs, 0)
 
 
+def _pos_list(pos, B):
+    """Per-sequence offsets as a list of B Python ints."""
+    if torch.is_tensor(pos):
+        pos = pos.tolist()
+    if isinstance(pos, int):
+        return [pos] * B
+    pos = [int(p) for p in pos]
+    assert len(pos) == B, "pos must hold one offset per sequence"
+    return pos
+
+
+def _append_ref_block(q, k_all, v_all, scale, pos):
+    """The s new queries (global positions pos..pos+s-1) against the T
+    rows of k_all/v_all: full visibility of the prefix, causal within the
+    new block. Plain torch ops, fp32 scores and softmax."""
+    B, H, s, D = q.shape
+    Hkv = k_all.size(1)
+    T = k_all.size(2)
+    G = H // Hkv
+    kf = k_all.float().repeat_interleave(G, dim=1)
+    vf = v_all.float().repeat_interleave(G, dim=1)
+    att = torch.matmul(q.float(), kf.transpose(-1, -2)) * scale
+    kv_pos = torch.arange(T, device=q.device)
+    q_pos = pos + torch.arange(s, device=q.device)
+    mask = kv_pos[None, :] <= q_pos[:, None]          # [s, T]
+    att = att.masked_fill(~mask, float("-inf"))
+    p = torch.softmax(att, dim=-1)
+    return torch.matmul(p, vf).to(q.dtype)
+
+
+def attn_append_ref(q, k_cache, v_cache, pos, scale):
+    """fp32 eager reference of attn_append, on whatever device the inputs
+    live. An int ``pos`` is one batched evaluation over the first
+    pos+Sq cache rows; per-sequence offsets loop over the sequences.
+    Cache rows >= pos+Sq are never touched."""
+    Sq = q.size(2)
+    if isinstance(pos, int):
+        return _append_ref_block(q, k_cache[:, :, :pos + Sq],
+                                 v_cache[:, :, :pos + Sq], scale, pos)
+    outs = []
+    for b, p in enumerate(_pos_list(pos, q.size(0))):
+        outs.append(_append_ref_block(
+            q[b:b + 1], k_cache[b:b + 1, :, :p + Sq],
+            v_cache[b:b + 1, :, :p + Sq], scale, p))
+    return torch.cat(outs, 0)
+
+
+def attn_append(q, k_cache, v_cache, pos, scale, max_len=None):
+    """Append attention: Sq new query rows per sequence at offset ``pos``
+    against the KV cache, which already holds the new rows at
+    pos .. pos+Sq-1. Query row i of sequence b attends to cache rows
+    0 .. pos[b]+i. The shape of speculative verification and of every
+    prefill chunk after the first; inference only (no gradient).
+
+    q: [B, H, Sq, 128] bf16; k_cache/v_cache: [B, Hkv, Lmax, 128] bf16,
+    passed whole (the kernel reads at the allocation stride and never
+    touches rows >= pos+Sq). ``pos``: a Python int (every sequence at the
+    same offset), a list, or an int tensor [B].
+    ``max_len`` bounds max(pos)+Sq and only sizes the split count;
+    None computes it, which costs a host read only when ``pos`` is a
+    device tensor — pass the cache capacity there to stay capturable.
+    GPU -> append.hip; CPU -> attn_append_ref.
+    """
+    if not q.is_cuda:
+        return attn_append_ref(q, k_cache, v_cache, pos, scale)
+    B, Sq = q.size(0), q.size(2)
+    if torch.is_tensor(pos):
+        if max_len is None:
+            max_len = int(pos.max().item()) + Sq
+        pos_t = pos.to(device=q.device, dtype=torch.int32).contiguous()
+    elif isinstance(pos, int):
+        if max_len is None:
+            max_len = pos + Sq
+        pos_t = torch.full((B,), pos, dtype=torch.int32, device=q.device)
+    else:
+        pos_l = _pos_list(pos, B)
+        if max_len is None:
+            max_len = max(pos_l) + Sq
+        pos_t = torch.tensor(pos_l, dtype=torch.int32, device=q.device)
+    return hip_ext().attn_append(q.contiguous(), k_cache, v_cache, pos_t,
+                                 max_len, scale)
+
+
 # ================================ adam =====================================
 def adamw_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.95, eps=1e-8,
                weight_decay=0.1, master=None, grad_scale=1.0):

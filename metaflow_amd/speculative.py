@@ -7,8 +7,13 @@ have chosen, then emit the target's own next token — per step at least
 one target token of progress, at most k+1). No reference counterpart
 (serving is a new capability, SURVEY §2.4 note); the MI355X angle is
 that verification replaces k launch-bound single-token decode steps
-with ONE k+1-token forward through the flash/cache attention path, so
-decode becomes compute-shaped instead of latency-shaped.
+with ONE k+1-token forward whose attention is the append kernel
+(ops/csrc/append.hip via K.attn_append: k+1 query rows at cache.pos > 0
+over the cache allocation), so decode becomes compute-shaped instead of
+latency-shaped. On CPU the verify forward and the single-token steps
+share one fp32 formula and the result is token-exact; on GPU the append
+kernel rounds P to bf16 for the MFMA where the decode kernel keeps it
+fp32, so a near-tied argmax may resolve differently between the two.
 
 Cache bookkeeping leans on KVCache.pos being the single read boundary
 (models/llama.py): rejected proposal rows stay in the cache allocation
