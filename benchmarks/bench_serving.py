@@ -3,7 +3,10 @@
 varlen flash-decode kernel), hipGraph replay vs eager decode.
 
     python benchmarks/bench_serving.py [--model llama3-8b] [--slots 8]
-        [--requests 24] [--prompt 256] [--new 64]
+        [--requests 24] [--prompt 256] [--new 64] [--pages N]
+
+--pages N serves the same request stream from a paged KV cache of N
+64-row pages (ContinuousBatcher(num_pages=N)) instead of dense slots.
 """
 
 import argparse
@@ -23,7 +26,8 @@ def run_one(model, graph, args, device):
     batcher = ContinuousBatcher(model, max_batch=args.slots,
                                 max_len=args.prompt + args.new + 8,
                                 graph=graph,
-                                prefill_chunk=args.prefill_chunk)
+                                prefill_chunk=args.prefill_chunk,
+                                num_pages=args.pages)
     random.seed(0)
     reqs = [batcher.submit(
         [random.randrange(2, 1000) for _ in
@@ -50,6 +54,9 @@ def main():
     p.add_argument("--new", type=int, default=64)
     p.add_argument("--prefill-chunk", type=int, default=None,
                    help="bound prompt tokens prefetched per step")
+    p.add_argument("--pages", type=int, default=None,
+                   help="serve from a paged KV cache with this many "
+                        "64-row pages (default: dense slots)")
     args = p.parse_args()
 
     import torch
@@ -72,7 +79,8 @@ def main():
             "config": {"model": args.model, "slots": args.slots,
                        "requests": args.requests,
                        "prompt_max": args.prompt, "new": args.new,
-                       "prefill_chunk": args.prefill_chunk},
+                       "prefill_chunk": args.prefill_chunk,
+                       "pages": args.pages},
         }), flush=True)
 
 

@@ -16,7 +16,9 @@ import torch
 import torch.nn as nn
 
 from ..ops import kernels as K
-from .llama import Linear, RMSNorm
+from .llama import (Linear, PagedKVCache, PagedSlotView, RMSNorm,
+                    decode_positions, paged_cached_attention,
+                    paged_decode_attention)
 
 
 @dataclass
@@ -267,7 +269,12 @@ class MixtralDecoderLayer(nn.Module):
                     cos_t, sin_t).transpose(1, 2)
         v = self.v_proj(y).view(B, S, cfg.num_kv_heads,
                                 cfg.head_dim).transpose(1, 2)
-        if cache is not None:
+        if isinstance(cache, PagedSlotView):
+            import math
+
+            o = paged_cached_attention(q, kk, v, cache, layer_idx,
+                                       1.0 / math.sqrt(cfg.head_dim))
+        elif cache is not None:
             kc, vc, pos = cache.k[layer_idx], cache.v[layer_idx], cache.pos
             kc[:, :, pos:pos + S] = kk
             vc[:, :, pos:pos + S] = v
@@ -313,12 +320,17 @@ class MixtralDecoderLayer(nn.Module):
         v = self.v_proj(y).view(B, 1, cfg.num_kv_heads, hd).transpose(1, 2)
         q = _rope_rows(q, c_rows, s_rows)
         k = _rope_rows(k, c_rows, s_rows)
-        kc, vc = cache.k[layer_idx], cache.v[layer_idx]
-        bidx = torch.arange(B, device=x.device)
-        kc[bidx, :, pos_t] = k[:, :, 0]
-        vc[bidx, :, pos_t] = v[:, :, 0]
-        o = K.attn_decode_varlen(q.contiguous(), kc, vc, lengths,
-                                 1.0 / math.sqrt(hd), max_len=max_len)
+        if isinstance(cache, PagedKVCache):
+            o = paged_decode_attention(q, k, v, cache, layer_idx, pos_t,
+                                       lengths, 1.0 / math.sqrt(hd),
+                                       max_len)
+        else:
+            kc, vc = cache.k[layer_idx], cache.v[layer_idx]
+            bidx = torch.arange(B, device=x.device)
+            kc[bidx, :, pos_t] = k[:, :, 0]
+            vc[bidx, :, pos_t] = v[:, :, 0]
+            o = K.attn_decode_varlen(q.contiguous(), kc, vc, lengths,
+                                     1.0 / math.sqrt(hd), max_len=max_len)
         o = o.transpose(1, 2).reshape(B, 1, cfg.num_heads * hd)
         x = res + self.o_proj(o)
         x = x + self.moe(self.post_norm(x))
@@ -374,13 +386,10 @@ class MixtralForCausalLM(nn.Module):
         MoE router's token dispatch is shape-dynamic — so the serving
         engine keeps Mixtral on the eager decode path
         (graph_safe_decode stays False)."""
-        from .llama import _rope_rows
-
-        pos_t = torch.as_tensor(positions, device=tokens.device,
-                                dtype=torch.long)
-        lengths = (pos_t + 1).to(torch.int32)
-        c_rows = self.cos_t[pos_t]
-        s_rows = self.sin_t[pos_t]
+        pos_t, lengths, rope_rows = decode_positions(cache, positions,
+                                                     tokens.device)
+        c_rows = self.cos_t[rope_rows]
+        s_rows = self.sin_t[rope_rows]
         x = self.embed(tokens)
         for li, layer in enumerate(self.layers):
             x = layer.decode_step(x, c_rows, s_rows, cache, li, pos_t,

@@ -13,6 +13,7 @@
 #include "attention.hip"
 #include "append.hip"
 #include "decode.hip"
+#include "paged.hip"
 #include "debug_kernels.hip"
 
 namespace {
@@ -509,6 +510,107 @@ torch::Tensor attn_append(torch::Tensor q, torch::Tensor kc,
   return o;
 }
 
+// ------------------------------------------------------- paged KV cache
+// Pool [num_pages, Hkv, 64, 128] and block table int32 [B, pages_per_seq]
+// (paged.hip). Neither call reads lengths / pos on the host: both are
+// hipGraph-capturable.
+void check_page_pool(const torch::Tensor& kp, const torch::Tensor& vp) {
+  check_bf16(kp, "k_pages");
+  check_bf16(vp, "v_pages");
+  TORCH_CHECK(kp.dim() == 4 && kp.size(2) == PG_ROWS && kp.size(3) == PG_D,
+              "page pool must be [num_pages, Hkv, 64, 128]");
+  TORCH_CHECK(vp.sizes() == kp.sizes(),
+              "k_pages and v_pages must have the same shape");
+}
+
+void check_block_table(const torch::Tensor& table, int B) {
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kInt32 &&
+              table.dim() == 2 && table.size(0) == B &&
+              table.is_contiguous(),
+              "block_table must be contiguous int32 [B, pages_per_seq] "
+              "on GPU");
+}
+
+torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kp,
+                                torch::Tensor vp, torch::Tensor table,
+                                torch::Tensor lengths, long max_len,
+                                double scale) {
+  check_bf16(q, "q");
+  check_page_pool(kp, vp);
+  TORCH_CHECK(q.dim() == 4 && q.size(2) == 1 && q.size(3) == PG_D,
+              "paged decode expects q [B,H,1,128]");
+  const int B = q.size(0), H = q.size(1);
+  const int num_pages = kp.size(0), Hkv = kp.size(1);
+  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  check_block_table(table, B);
+  const int table_stride = table.size(1);
+  TORCH_CHECK(max_len >= 1 && max_len <= (long)table_stride * PG_ROWS,
+              "max_len must be in [1, 64 * pages_per_seq]");
+  TORCH_CHECK(lengths.is_cuda() &&
+              lengths.scalar_type() == torch::kInt32 &&
+              lengths.numel() == B && lengths.is_contiguous(),
+              "lengths must be int32 [B] on GPU");
+  // attn_decode_varlen's split count (fill 256 CUs at small B*H, chunks
+  // >= ~256 rows), capped by the page count: a split is whole pages
+  int splits = (int)std::max<long>(1, 1024 / ((long)B * H));
+  splits = (int)std::min<long>(splits, (max_len + 255) / 256);
+  splits = (int)std::min<long>(splits,
+                               (max_len + PG_ROWS - 1) / PG_ROWS);
+  splits = std::max(splits, 1);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto o_part = torch::empty({splits, B, H, 128}, f32);
+  auto ml_part = torch::empty({splits, B, H, 2}, f32);
+  auto o = torch::empty_like(q);
+  dim3 grid(splits, H, B);
+  attn_decode_paged_partial_kernel<<<grid, 256, 0, cur_stream()>>>(
+      bf(q), bf(kp), bf(vp), table.data_ptr<int>(),
+      lengths.data_ptr<int>(), o_part.data_ptr<float>(),
+      ml_part.data_ptr<float>(), B, H, Hkv, num_pages, table_stride,
+      splits, (float)scale);
+  HIP_CHECK_KERNEL();
+  attn_decode_merge_kernel<<<B * H, 64, 0, cur_stream()>>>(
+      o_part.data_ptr<float>(), ml_part.data_ptr<float>(), bfm(o), B, H,
+      splits);
+  HIP_CHECK_KERNEL();
+  return o;
+}
+
+// k, v [B, Hkv, S, 128] may be strided views (last dim dense, 16-byte
+// aligned rows): the decode step's K/V are slices of the QKV GEMM output
+void check_new_rows(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16,
+              name, " must be bf16 on GPU");
+  TORCH_CHECK(t.dim() == 4 && t.size(3) == PG_D && t.stride(3) == 1,
+              name, " must be [B,Hkv,S,128] with a dense last dim");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+              t.stride(2) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " rows must be 16-byte aligned");
+}
+
+void kv_page_write(torch::Tensor k, torch::Tensor v, torch::Tensor kp,
+                   torch::Tensor vp, torch::Tensor table,
+                   torch::Tensor pos) {
+  check_new_rows(k, "k");
+  check_new_rows(v, "v");
+  check_page_pool(kp, vp);
+  TORCH_CHECK(v.sizes() == k.sizes(), "k and v must have the same shape");
+  const int B = k.size(0), Hkv = k.size(1), S = k.size(2);
+  TORCH_CHECK(kp.size(1) == Hkv, "k and the pool disagree on Hkv");
+  check_block_table(table, B);
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
+              pos.numel() == B && pos.is_contiguous(),
+              "pos must be int32 [B] on GPU");
+  const long long vecs = (long long)B * Hkv * S * (PG_D / 8);
+  if (vecs == 0) return;
+  kv_page_write_kernel<<<grid_for(vecs), kBlock, 0, cur_stream()>>>(
+      bf(k), bf(v), bfm(kp), bfm(vp), table.data_ptr<int>(),
+      pos.data_ptr<int>(), B, Hkv, S, (int)kp.size(0), (int)table.size(1),
+      k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
+      v.stride(2));
+  HIP_CHECK_KERNEL();
+}
+
 // ------------------------------------------------------- layout probes
 torch::Tensor dbg_mfma32(torch::Tensor a, torch::Tensor b) {
   auto out = torch::empty({32, 32}, a.options().dtype(torch::kFloat32));
@@ -571,6 +673,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_append", &attn_append,
         "append attention: Sq query rows at per-sequence offsets pos "
         "(int32 [B]) over the KV cache (q [B,H,Sq,128])");
+  m.def("attn_decode_paged", &attn_decode_paged,
+        "flash-decode over a paged KV cache: pool [P,Hkv,64,128], block "
+        "table int32 [B,pages], lengths int32 [B] (0 = output 0)");
+  m.def("kv_page_write", &kv_page_write,
+        "scatter new K/V rows [B,Hkv,S,128] into the page pool at "
+        "pos[b].. through the block table (pos < 0 skips the sequence)");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");

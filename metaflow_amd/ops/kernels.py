@@ -598,6 +598,97 @@ def attn_append(q, k_cache, v_cache, pos, scale, max_len=None):
                                  max_len, scale)
 
 
+# ============================ paged KV cache ===============================
+#: rows per page — a compile-time constant of paged.hip (the row tile one
+#: wave owns in the decode kernels)
+PAGE_ROWS = 64
+
+
+def kv_page_gather(pages, table_row, n):
+    """The first ``n`` rows of one sequence as a contiguous
+    [1, Hkv, n, 128] tensor. pages: [num_pages, Hkv, 64, 128];
+    table_row: the sequence's block-table row (int tensor on the pool's
+    device). Plain torch indexing on both devices — the cold path (later
+    prefill chunks on a paged cache), not a kernel."""
+    npg = (n + PAGE_ROWS - 1) // PAGE_ROWS
+    idx = table_row[:npg].to(device=pages.device, dtype=torch.long)
+    g = pages[idx]                                  # [npg, Hkv, 64, 128]
+    g = g.permute(1, 0, 2, 3).reshape(1, pages.size(1), npg * PAGE_ROWS,
+                                      pages.size(3))
+    return g[:, :, :n].contiguous()
+
+
+def attn_decode_paged(q, k_pages, v_pages, block_table, lengths, scale,
+                      max_len):
+    """Flash-decode over a paged KV cache: one query row per (b, h)
+    against the first lengths[b] rows of sequence b, found through the
+    block table (length 0 = inactive slot, output row zero).
+
+    q: [B, H, 1, 128] bf16; k_pages/v_pages: [num_pages, Hkv, 64, 128]
+    bf16; block_table: int32 [B, pages_per_seq], entry [b, j] = pool page
+    of rows 64j..64j+63 (-1 = none; only entries j < ceil(len_b/64) are
+    read); lengths: int32 [B] (GPU) or list/IntTensor. ``max_len`` (the
+    cache capacity) sizes the split count, so lengths is never read on
+    the host and the call is always hipGraph-capturable.
+    GPU -> paged.hip; CPU -> gather through the table + fp32 reference.
+    """
+    if q.is_cuda:
+        if not torch.is_tensor(lengths):
+            lengths = torch.tensor(lengths, dtype=torch.int32,
+                                   device=q.device)
+        lengths = lengths.to(device=q.device,
+                             dtype=torch.int32).contiguous()
+        return hip_ext().attn_decode_paged(
+            q.contiguous(), k_pages, v_pages, block_table, lengths,
+            max_len, scale)
+    outs = []
+    for b in range(q.size(0)):
+        n = int(lengths[b])
+        if n == 0:
+            outs.append(torch.zeros_like(q[b:b + 1]))
+            continue
+        outs.append(attention_ref(
+            q[b:b + 1], kv_page_gather(k_pages, block_table[b], n),
+            kv_page_gather(v_pages, block_table[b], n), scale,
+            causal=False))
+    return torch.cat(outs, 0)
+
+
+def _rows16(t):
+    """t as the page-write kernel reads it: dense last dim, every row
+    16-byte aligned (copies only when a view breaks that)."""
+    if t.stride(-1) != 1 or any(s % 8 for s in t.stride()[:-1]) \
+            or t.data_ptr() % 16:
+        return t.contiguous()
+    return t
+
+
+def kv_page_write(k, v, k_pages, v_pages, block_table, pos):
+    """Write new rows k, v [B, Hkv, S, 128] into the page pool, in place,
+    at rows pos[b] .. pos[b]+S-1 of sequence b through the block table
+    (rows may cross page boundaries). pos: int32 [B] (a device tensor on
+    GPU — never read on the host) or a list; pos[b] < 0 skips sequence b
+    entirely (inactive and mid-prefill slots).
+    GPU -> paged.hip, K and V in one launch; CPU -> index assignment."""
+    if k.is_cuda:
+        if not torch.is_tensor(pos):
+            pos = torch.tensor(pos, dtype=torch.int32, device=k.device)
+        pos = pos.to(device=k.device, dtype=torch.int32).contiguous()
+        hip_ext().kv_page_write(_rows16(k), _rows16(v), k_pages, v_pages,
+                                block_table, pos)
+        return
+    S = k.size(2)
+    for b, p in enumerate(_pos_list(pos, k.size(0))):
+        if p < 0:
+            continue
+        for s in range(S):
+            page = int(block_table[b, (p + s) // PAGE_ROWS])
+            assert page >= 0, "write to a row that has no page"
+            r = (p + s) % PAGE_ROWS
+            k_pages[page, :, r] = k[b, :, s]
+            v_pages[page, :, r] = v[b, :, s]
+
+
 # ================================ adam =====================================
 def adamw_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.95, eps=1e-8,
                weight_decay=0.1, master=None, grad_scale=1.0):

@@ -14,7 +14,10 @@ our own kernels — no reference counterpart, SURVEY §2.4 note):
   per-slot cache scatter, models/llama.py decode_step);
 * finished slots free immediately and the queue refills them, so
   throughput tracks the arrival rate instead of the slowest member of a
-  static batch.
+  static batch;
+* opt-in paging (``num_pages``): the slots share a pool of 64-row pages
+  through a device block table instead of reserving max_len rows each
+  (models/llama.py PagedKVCache, paged.hip).
 
 Greedy decoding is token-exact with ``model.generate`` per request.
 """
@@ -46,7 +49,7 @@ class _SlotView(object):
 
 class ContinuousBatcher(object):
     def __init__(self, model, max_batch=8, max_len=2048, graph="auto",
-                 prefill_chunk=None):
+                 prefill_chunk=None, num_pages=None):
         """graph: capture the whole decode step in a hipGraph and replay
         it per token (decode is LAUNCH-bound — ~200 small kernels per
         step; replay collapses them to one submit). "auto" captures on
@@ -61,18 +64,36 @@ class ContinuousBatcher(object):
         prefill (a slot mid-prefill sits at cache length
         positions[slot] and its decode row is masked by the varlen
         kernel's per-slot lengths). None = whole-prompt prefill at
-        admission (lowest total latency when prompts are short)."""
+        admission (lowest total latency when prompts are short).
+
+        num_pages: None keeps the dense cache (max_len rows reserved per
+        slot). An integer selects the paged cache instead: a pool of
+        that many 64-row pages shared by all slots (models/llama.py
+        PagedKVCache, ops/csrc/paged.hip), so the number of concurrent
+        requests is bounded by the rows they can actually reach, not by
+        max_batch * max_len. Admission is FIFO and reserves
+        ceil((len(prompt) + max_new) / 64) pages for the head request —
+        it waits (and everything behind it) until they fit, so no
+        request runs out of pages mid-decode and nothing is preempted.
+        Physical pages are allocated lazily as rows are written."""
         import torch
 
-        from .models.llama import KVCache
+        from .models.llama import KVCache, PagedKVCache
 
         self.model = model
         self.max_batch = max_batch
         self.max_len = max_len
         device = next(model.parameters()).device
         self.device = device
-        self.cache = KVCache(model.cfg, max_batch, max_len, device,
-                             dtype=model.embed.weight.dtype)
+        self.paged = num_pages is not None
+        if self.paged:
+            self.cache = PagedKVCache(model.cfg, num_pages, max_batch,
+                                      max_len, device,
+                                      dtype=model.embed.weight.dtype)
+            self._reserved = [0] * max_batch  # pages reserved per slot
+        else:
+            self.cache = KVCache(model.cfg, max_batch, max_len, device,
+                                 dtype=model.embed.weight.dtype)
         self.positions = [0] * max_batch    # cached tokens per slot
         self.slots = [None] * max_batch     # Request or None
         self.next_token = [0] * max_batch   # token to feed next step
@@ -102,6 +123,8 @@ class ContinuousBatcher(object):
                                     device=self.device)
         self._pos_buf = torch.zeros(self.max_batch, dtype=torch.long,
                                     device=self.device)
+        if self.paged:
+            self._pos_buf.fill_(-1)  # no slot takes part while capturing
         # warmup on a side stream (allocator primes its graph pool)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -126,6 +149,11 @@ class ContinuousBatcher(object):
                                                 device=self.device))
             self._graph.replay()
             return self._logits_buf
+        if self.paged:
+            # capacity-sized splits, as in the captured step: eager and
+            # replayed decodes launch identical grids
+            return self.model.decode_step(tokens, self.cache, positions,
+                                          max_len=self.max_len)
         return self.model.decode_step(tokens, self.cache, positions)
 
     def submit(self, prompt_tokens, max_new_tokens):
@@ -134,23 +162,55 @@ class ContinuousBatcher(object):
         return req
 
     # ------------------------------------------------------------- internals
+    def _view(self, slot):
+        if self.paged:
+            from .models.llama import PagedSlotView
+
+            return PagedSlotView(self.cache, slot)
+        return _SlotView(self.cache, slot)
+
+    def _reserve_head(self, slot):
+        """Paged admission of the queue's head into ``slot``: reserve
+        every page the request can ever touch, or leave it waiting."""
+        req = self.queue[0]
+        total = len(req.prompt) + req.max_new
+        assert total <= self.max_len, \
+            "request longer than the slot capacity"
+        need = -(-total // self.cache.PAGE)
+        assert need <= self.cache.num_pages, \
+            "request larger than the page pool"
+        if not self.cache.reserve(need):
+            return False
+        self._reserved[slot] = need
+        return True
+
+    def _ensure_rows(self, slot, n_rows):
+        """Paged cache: give ``slot`` the pages for rows 0 .. n_rows-1
+        before a prefill writes them (no-op on the dense cache)."""
+        if self.paged:
+            self.cache.ensure(slot, n_rows)
+            self.cache.sync()
+
     def _admit(self):
         torch = self._torch
         for slot in range(self.max_batch):
             if self.slots[slot] is not None or not self.queue:
                 continue
+            if self.paged and not self._reserve_head(slot):
+                return  # FIFO: nobody overtakes the waiting head
             req = self.queue.popleft()
             assert len(req.prompt) + req.max_new <= self.max_len, \
                 "request longer than the slot capacity"
             self.slots[slot] = req
             if self.prefill_chunk is not None:
                 # chunked: cache nothing yet; step() feeds chunks
-                self._views[slot] = _SlotView(self.cache, slot)
+                self._views[slot] = self._view(slot)
                 self._prefill_done[slot] = 0
                 self.positions[slot] = 0
                 continue
             prompt = torch.tensor([req.prompt], device=self.device)
-            view = _SlotView(self.cache, slot)
+            view = self._view(slot)
+            self._ensure_rows(slot, len(req.prompt))
             with torch.no_grad():
                 logits = self.model(prompt, cache=view)
             nxt = int(logits[0, -1].float().argmax())
@@ -173,6 +233,7 @@ class ContinuousBatcher(object):
             a = self._prefill_done[slot]
             b = min(a + self.prefill_chunk, len(req.prompt))
             chunk = torch.tensor([req.prompt[a:b]], device=self.device)
+            self._ensure_rows(slot, b)
             with torch.no_grad():
                 logits = self.model(chunk, cache=view)
             self._prefill_done[slot] = b
@@ -187,6 +248,10 @@ class ContinuousBatcher(object):
                 self._finish(slot)
 
     def _finish(self, slot):
+        if self.paged:
+            self.cache.free_slot(slot)
+            self.cache.release_reservation(self._reserved[slot])
+            self._reserved[slot] = 0
         self.slots[slot].done = True
         self.slots[slot] = None
         self.positions[slot] = 0
@@ -213,6 +278,15 @@ class ContinuousBatcher(object):
                 pos_list[i] = self._prefill_done[i]
         if not active:
             return 0
+        if self.paged:
+            # no garbage-row trick here: slots that take no part pass
+            # -1 (nothing written, length 0); a slot about to write the
+            # first row of a page gets that page now
+            pos_list = [-1] * self.max_batch
+            for i in active:
+                pos_list[i] = self.positions[i]
+                self.cache.ensure(i, self.positions[i] + 1)
+            self.cache.sync()
         tokens = torch.zeros(self.max_batch, 1, dtype=torch.long,
                              device=self.device)
         for i in active:
