@@ -12,8 +12,10 @@
 //    serial max/sum over the lane's 16 C registers per 32-row sub-tile
 //    plus one shfl_xor(32) — no cross-lane group reductions, no LDS
 //    round-trip for P;
-//  * P / dS become the A operand of the second GEMM in-register
-//    (col_to_afrags: packed bf16 pairs + one shfl_xor(32) exchange);
+//  * P / dS become an operand of the second GEMM in-register: the A
+//    operand in fwd and dq (col_to_afrags: packed bf16 pairs + one
+//    shfl_xor(32) exchange), the B operand of the transposed product in
+//    dkdv (acc_to_bfrags: the pack + a v_permlane32_swap half exchange);
 //  * LDS holds only the streamed operand tiles, in the 16-wide PANEL
 //    layout below, which serves contiguous A-fragment reads and
 //    hardware-transposed B-fragment reads from the same copy.
@@ -545,17 +547,107 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
 // writes FP32 PARTIALS laid out [B, H, S, D]; dkdv_reduce_kernel sums
 // the G partials per kv head and converts to bf16 — numerically
 // identical to the old in-register fp32 accumulation across g. 8 waves
-// x 32 kv rows; K/V rows stay register-resident (the compiler hoists
-// them at the 256-VGPR budget, 0 spill — guarded by
-// tests/test_attn_kernel_resources.py). LDS: Q and dO panel tiles
-// (2 x 16 KiB) + 64 lse + 64 delta floats = 33280 bytes.
+// x 32 kv rows. LDS: Q and dO panel tiles (2 x 16 KiB) + 64 lse + 64
+// delta floats = 33280 bytes.
 //
-// This kernel sits EXACTLY at the register limit, and its code generation
-// is fragile: taking the coordinates from wave_coord(), the transposed
-// reads from tr_load_bfrags or the epilogue from store_acc_tile each
-// changed its SGPR count, its compiler-placed waits or its epilogue
-// length. It therefore keeps those three pieces open-coded; they must
-// stay in step with the helpers above.
+// KEY ON THE LANE. S = Q·K^T and dP = dO·V^T come out as C[q][kv]: the
+// lane is the kv row, the 16 registers are q rows. That is already the
+// B-operand shape of the TRANSPOSED products
+//   dV^T(d x kv) += dO^T(d x q) · P(q x kv),  dK^T += Q^T · dS,
+// so P and dS need the pairwise bf16 pack and a half exchange between the
+// lane halves in the register file (acc_to_bfrags) — no ds_bpermute, no
+// LDS. The exchange restores the natural k order, which keeps the
+// results bit-identical to the dV = P^T·dO form; tests/
+// test_attn_dkdv_exact_gpu.py checks the operand pairing with exact
+// integers.
+// The accumulators hold d on the rows and kv on the lane; the epilogue
+// transposes them through the (by then free) Q/dO tiles so the partials
+// keep their [B,H,S,D] rows and 128-byte store segments.
+//
+// K/V RESIDENCY. The wave's 32 K rows and 32 V rows (64 VGPRs as B
+// fragments) are loaded ONCE before the q sweep. Plain loads are not
+// enough: the compiler treats them as rematerialisable and, at the
+// 256-VGPR limit, puts all 32 global loads back inside the tile loop
+// (the earlier version of this kernel did exactly that under a comment
+// that claimed residency). The empty asm after the loads makes the values
+// opaque, so they either stay in registers or show up as spills, which
+// tests/test_attn_kernel_resources.py forbids; tests/test_dkdv_loop_asm.py
+// counts the loop's global loads.
+//
+// Code generation here is fragile (register limit): the coordinates, the
+// transposed-read addressing and the epilogue stay open-coded rather than
+// going through wave_coord() / tr_load_bfrags / store_acc_tile.
+
+// C tile (column on the lane, rows in the registers) -> the two bf16 B
+// fragments (k-steps of 16 rows) of a product that sums over its rows.
+// Packed pairwise, lane half hi holds rows 16s + {0..3, 8..11} + 4hi of
+// step s; two v_permlane32_swap per step (a register-file half exchange,
+// no LDS) trade the lower half's rows 8..11 for the upper half's rows
+// 4..7, so element j of lane half hi is row 16s + 8hi + j: the NATURAL k
+// order. That keeps every product in the k slot it has in dV = P^T·dO /
+// dK = dS^T·Q, so the fp32 sums are bit-identical to that form; feeding
+// the packed registers unswapped (permuted k order) is also a valid
+// operand but changes the order in which an MFMA adds its 16 products.
+DEV void acc_to_bfrags(const f16f& x, bf16x8* pb) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    unsigned int w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      w[i] = pack_bf2(x[8 * s + 2 * i], x[8 * s + 2 * i + 1]);
+    union {
+      unsigned int w[4];
+      bf16x8 v;
+    } u;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      auto r = __builtin_amdgcn_permlane32_swap(w[i], w[2 + i], false,
+                                                false);
+      u.w[i] = r[0];
+      u.w[2 + i] = r[1];
+    }
+    pb[s] = u.v;
+  }
+}
+
+// Lanes of one wave exchanging data through LDS: the hardware runs a
+// wave's DS instructions in order, but the compiler's per-lane alias
+// analysis may move a read above the partner lane's write unless fenced.
+DEV void lds_wave_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Store a wave's transposed accumulators (acc[n][r] = X[kv = l32][d =
+// n*32 + c_row(r, hi)]) as 32 rows of a row-major [rows][128] fp32 array:
+// one 32 x 32 block at a time through the wave's own 4 KiB of LDS, XOR-
+// swizzled so both the column writes and the row reads are conflict-free.
+// Each store instruction covers two rows x 128 contiguous bytes.
+DEV void store_acc_tile_t(float* dst, long long off0, float* tw,
+                          const f16f acc[4], int l32, int hi) {
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int dl = (r & 3) + 8 * (r >> 2) + 4 * hi;
+      tw[l32 * 32 + (dl ^ l32)] = acc[n][r];
+    }
+    lds_wave_fence();
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = 2 * i + hi;
+      dst[off0 + (long long)row * ATT_D + n * 32 + l32] =
+          tw[row * 32 + (l32 ^ row)];
+    }
+    lds_wave_fence();
+  }
+}
+
+// dynamic LDS of the dkdv kernel: the block's 256 V rows, 64 KiB
+// (DKDV_DYN_LDS at the launch site); the static arrays end 16-byte aligned
+extern __shared__ __attribute__((aligned(16))) short dkdv_v_img[];
+#define DKDV_DYN_LDS (256 * ATT_D * 2)
 
 template <int BLOCK>
 __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
@@ -584,10 +676,25 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
   const long long kvoff =
       (((long long)b * Hkv + hk) * S + kvb * BKVB) * ATT_D;
 
-  // K/V rows for this wave's 32 kv rows; register-resident across the
-  // whole q loop at the 256-VGPR budget
-  const short* krow = k + kvoff + (long long)(wid * 32 + l32) * ATT_D;
-  const short* vrow = v + kvoff + (long long)(wid * 32 + l32) * ATT_D;
+  // this lane's K row as B fragments in registers and its V row in the
+  // dynamic LDS image, both resident for the whole q sweep (K/V
+  // RESIDENCY above). The image is [wave][8 panels][32 rows][16]: a
+  // lane's fragment s sits at s*512 + lane*8 shorts, so every wave read
+  // is 1 KiB contiguous, and each lane reads back only what it wrote
+  // itself — no barrier.
+  bf16x8 kr[8];
+  short* vimg = dkdv_v_img + wid * (32 * ATT_D) + lane * 8;
+  {
+    const short* krow = k + kvoff + (long long)(wid * 32 + l32) * ATT_D;
+    const short* vrow = v + kvoff + (long long)(wid * 32 + l32) * ATT_D;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      kr[s] = *(const bf16x8*)(krow + s * 16 + hi * 8);
+      *(bf16x8*)(vimg + s * 512) = *(const bf16x8*)(vrow + s * 16 + hi * 8);
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) asm volatile("" : "+v"(kr[s]));
+  }
 
   f16f acc_dk[4], acc_dv[4];
 #pragma unroll
@@ -613,7 +720,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
     // wave-uniform skip: all of this wave's kv rows above every q row
     if (causal && jq * BQ2 + BQ2 - 1 < kvb * BKVB + wid * 32) continue;
 
-    // per 32-q sub-tile: S, dP, P/dS, dV, dK — keeps live regs low
+    // per 32-q sub-tile: S, dP, P/dS, dV^T, dK^T — keeps live regs low
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       f16f st = (f16f){}, dpt = (f16f){};
@@ -621,17 +728,14 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
       for (int s = 0; s < 8; ++s) {
         bf16x8 qf = frag8_panel<BQ2>(qp, t * 32 + l32, s * 16 + hi * 8);
         bf16x8 df = frag8_panel<BQ2>(dop, t * 32 + l32, s * 16 + hi * 8);
-        bf16x8 kr = *(const bf16x8*)(krow + s * 16 + hi * 8);
-        bf16x8 vr = *(const bf16x8*)(vrow + s * 16 + hi * 8);
-        st = mfma32(qf, kr, st);
-        dpt = mfma32(df, vr, dpt);
+        bf16x8 vf = *(const bf16x8*)(vimg + s * 512);
+        st = mfma32(qf, kr[s], st);
+        dpt = mfma32(df, vf, dpt);
       }
       // P (into st) with causal mask q >= kv; dS (into dpt). lse/delta
       // come as f32x4 GROUP loads: the per-element lse_s[qrl] reads were
       // 64 scalar ds_read_b32 per tile (the dq kernel holds its lse in
-      // a register) — the disassembly showed them, plus their waitcnts,
-      // matching the mfma count, which is where dkdv's efficiency gap
-      // vs dq was hiding. qrl = t*32 + c_row(r, hi), so r = g*4+j walks
+      // a register). qrl = t*32 + c_row(r, hi), so r = g*4+j walks
       // 4 consecutive floats at t*32 + 8g + 4hi.
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -649,18 +753,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
           dpt[r] = p * (dpt[r] - dl[j]) * scale;
         }
       }
-      // dV(32kv x 128d) += P^T(32kv x 32q) @ dO(32q x 128d), then
-      // dK += dS^T @ Q — FOUR transposed-read groups, software-pipelined
-      // with COUNTED waits: group g+1's 8 DS reads issue before waiting
-      // on group g (DS returns in order, so lgkmcnt(8) = "the earlier 8
-      // are done"), so the transpose-read latency of every group but
-      // the last hides under the previous group's MFMAs. A counter run
-      // showed both backward kernels stalled on these full-stop groups,
-      // not on LDS bandwidth (LdsUtil 12%, conflicts 4%).
-      bf16x8 pa[2], pak[2];
-      col_to_afrags<1>(&st, pa, hi);
+      // dV^T(128d x 32kv) += dO^T(128d x 32q) @ P(32q x 32kv), then
+      // dK^T += Q^T @ dS — FOUR transposed-read groups (one 16-q k-step
+      // each), software-pipelined with COUNTED waits: group g+1's 8 DS
+      // reads issue before waiting on group g (DS returns in order, so
+      // lgkmcnt(8) = "the earlier 8 are done"), so the transpose-read
+      // latency of every group but the last hides under the previous
+      // group's MFMAs.
+      bf16x8 pb[2], pbk[2];
+      acc_to_bfrags(st, pb);
       BFrag bfr[2][4];
-      // same addressing as tr_load_bfrags<BQ2> (derivation there)
+      // same addressing as tr_load_bfrags<BQ2> (derivation there); the
+      // fragments serve as the A operand dO^T / Q^T
       const int tr_lane_off = (((lane >> 2) & 3) * 16) + (lane & 3) * 4;
       const int tr_panel = ((lane >> 4) & 1) * (BQ2 * 16);
       const short* g_tile[4] = {dop, dop, qp, qp};
@@ -676,7 +780,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
         bfr[0][n].u[0] = tr_read(g_tile[0] + base);
         bfr[0][n].u[1] = tr_read(g_tile[0] + base + 4 * 16);
       }
-      col_to_afrags<1>(&dpt, pak, hi);  // VALU under the first DS group
+      acc_to_bfrags(dpt, pbk);  // VALU under the first DS group
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int cur = g & 1;
@@ -693,29 +797,24 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
           asm volatile("s_waitcnt lgkmcnt(0)");
         }
         __builtin_amdgcn_sched_barrier(0);
-        const bf16x8 a = (g < 2) ? pa[g] : pak[g - 2];
+        const bf16x8 bop = (g < 2) ? pb[g] : pbk[g - 2];
         f16f* acc = (g < 2) ? acc_dv : acc_dk;
 #pragma unroll
         for (int n = 0; n < 4; ++n)
-          acc[n] = mfma32(a, bfr[cur][n].v, acc[n]);
+          acc[n] = mfma32(bfr[cur][n].v, bop, acc[n]);
       }
     }
   }
 
-  // epilogue: fp32 partials at [b, h, kv row, d]; row formula written
-  // out for the same reason as in dq
-  const long long poff = (hoff + (long long)kvb * BKVB) * ATT_D;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row_local = (r & 3) + 8 * (r >> 2) + 4 * hi;
-    const long long obase =
-        poff + (long long)(wid * 32 + row_local) * ATT_D;
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      dk_part[obase + n * 32 + l32] = acc_dk[n][r];
-      dv_part[obase + n * 32 + l32] = acc_dv[n][r];
-    }
-  }
+  // epilogue: fp32 partials at [b, h, kv row, d]. Every wave is done with
+  // the Q/dO tiles after the barrier; each then transposes through its
+  // own 4 KiB of them.
+  __syncthreads();
+  float* tw = (float*)(wid < 4 ? qp : dop) + (wid & 3) * 1024;
+  const long long poff =
+      (hoff + (long long)kvb * BKVB + wid * 32) * ATT_D;
+  store_acc_tile_t(dk_part, poff, tw, acc_dk, l32, hi);
+  store_acc_tile_t(dv_part, poff, tw, acc_dv, l32, hi);
 }
 
 // Sum the G per-q-head fp32 partials into the kv head's bf16 (dK, dV).

@@ -380,7 +380,23 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
         bf(dout), bf(o), delta.data_ptr<float>(), rows);
     HIP_CHECK_KERNEL();
   }
-  attn_bwd_dkdv_v2_kernel<512><<<grid, 512, 0, cur_stream()>>>(
+  {
+    // static 33280 B + the 64 KiB V image exceed the 64 KiB a kernel gets
+    // without asking; the attribute is per device
+    static bool lds_set[64] = {};
+    int dev_id = 0;
+    TORCH_CHECK(hipGetDevice(&dev_id) == hipSuccess && dev_id < 64,
+                "attn_bwd: hipGetDevice failed");
+    if (!lds_set[dev_id]) {
+      hipError_t e = hipFuncSetAttribute(
+          reinterpret_cast<const void*>(&attn_bwd_dkdv_v2_kernel<512>),
+          hipFuncAttributeMaxDynamicSharedMemorySize, DKDV_DYN_LDS);
+      TORCH_CHECK(e == hipSuccess, "attn_bwd: cannot raise dynamic LDS: ",
+                  hipGetErrorString(e));
+      lds_set[dev_id] = true;
+    }
+  }
+  attn_bwd_dkdv_v2_kernel<512><<<grid, 512, DKDV_DYN_LDS, cur_stream()>>>(
       bf(q), bf(k), bf(v), bf(dout), lse.data_ptr<float>(),
       delta.data_ptr<float>(), dk_part.data_ptr<float>(),
       dv_part.data_ptr<float>(), B, H, Hkv, S, (float)scale, icausal);
