@@ -325,9 +325,9 @@ def paged_cached_attention(q, k, v, view, layer_idx, scale):
     """Attention of a batch-1 forward over a PagedSlotView: write the S
     new K/V rows at view.pos, then attend. The first chunk (pos 0) is
     the flash prefill on the fresh tensors; a one-token step is the paged
-    decode kernel; a later chunk gathers the slot's rows into a
-    contiguous prefix and runs the append kernel on it (there is no
-    block-table append kernel — the gather is this path's extra cost)."""
+    decode kernel; a later chunk is the paged append kernel, which reads
+    the slot's pages in place through the block table
+    (append_paged.hip)."""
     pc, slot, pos = view.paged, view.slot, view.pos
     S = q.size(2)
     assert q.size(0) == 1, "a paged slot view holds one sequence"
@@ -339,9 +339,8 @@ def paged_cached_attention(q, k, v, view, layer_idx, scale):
     if S == 1:
         return K.attn_decode_paged(q.contiguous(), kp, vp, table_row,
                                    [pos + 1], scale, pc.max_len)
-    kg = K.kv_page_gather(kp, table_row[0], pos + S)
-    vg = K.kv_page_gather(vp, table_row[0], pos + S)
-    return K.attn_append(q.contiguous(), kg, vg, pos, scale)
+    return K.attn_append_paged(q.contiguous(), kp, vp, table_row, [pos],
+                               scale)
 
 
 def decode_positions(cache, positions, device):

@@ -14,6 +14,7 @@
 #include "append.hip"
 #include "decode.hip"
 #include "paged.hip"
+#include "append_paged.hip"
 #include "debug_kernels.hip"
 
 namespace {
@@ -591,6 +592,70 @@ torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kp,
   return o;
 }
 
+// Append attention through the block table (append_paged.hip): Sq new
+// query rows per sequence at device-side offsets pos[b] (pos[b] < 0 = the
+// sequence takes no part, output 0). max_len bounds max(pos) + Sq and
+// only sizes the split count: neither pos nor the table is read here.
+torch::Tensor attn_append_paged(torch::Tensor q, torch::Tensor kp,
+                                torch::Tensor vp, torch::Tensor table,
+                                torch::Tensor pos, long max_len,
+                                double scale) {
+  check_bf16(q, "q");
+  check_page_pool(kp, vp);
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == PG_D && q.size(2) >= 1,
+              "paged append expects q [B,H,Sq,128]");
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2);
+  const int num_pages = kp.size(0), Hkv = kp.size(1);
+  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  check_block_table(table, B);
+  const int table_stride = table.size(1);
+  TORCH_CHECK(max_len >= 1 && max_len <= (long)table_stride * PG_ROWS,
+              "max_len must be in [1, 64 * pages_per_seq]");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
+              pos.numel() == B && pos.is_contiguous(),
+              "pos must be int32 [B] on GPU");
+  // attn_append's launch, verbatim: one wave (32 query rows) for the
+  // verify block, four for a chunk; enough workgroups to fill 256 CUs,
+  // chunks of >= ~256 cache rows
+  const bool small = Sq <= 32;
+  const int bq = small ? 32 : 128;
+  const int q_tiles = (Sq + bq - 1) / bq;
+  const long wgs = (long)B * H * q_tiles;
+  int splits = (int)std::max<long>(1, (small ? 1024 : 512) / wgs);
+  splits = (int)std::min<long>(splits, (max_len + 255) / 256);
+  splits = std::max(splits, 1);
+  auto o = torch::empty_like(q);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  torch::Tensor o_part, ml_part;
+  float* o_part_p = nullptr;
+  float* ml_part_p = nullptr;
+  if (splits > 1) {
+    o_part = torch::empty({splits, B, H, Sq, 128}, f32);
+    ml_part = torch::empty({splits, B, H, Sq, 2}, f32);
+    o_part_p = o_part.data_ptr<float>();
+    ml_part_p = ml_part.data_ptr<float>();
+  }
+  dim3 grid(q_tiles * splits, H, B);
+  if (small)
+    attn_append_paged_kernel<1><<<grid, 64, 0, cur_stream()>>>(
+        bf(q), bf(kp), bf(vp), table.data_ptr<int>(), pos.data_ptr<int>(),
+        bfm(o), o_part_p, ml_part_p, B, H, Hkv, Sq, num_pages,
+        table_stride, splits, (float)scale);
+  else
+    attn_append_paged_kernel<4><<<grid, 256, 0, cur_stream()>>>(
+        bf(q), bf(kp), bf(vp), table.data_ptr<int>(), pos.data_ptr<int>(),
+        bfm(o), o_part_p, ml_part_p, B, H, Hkv, Sq, num_pages,
+        table_stride, splits, (float)scale);
+  HIP_CHECK_KERNEL();
+  if (splits > 1) {
+    const long long R = (long long)B * H * Sq;
+    attn_append_merge_kernel<<<(int)((R + 3) / 4), 256, 0, cur_stream()>>>(
+        o_part_p, ml_part_p, bfm(o), R, splits);
+    HIP_CHECK_KERNEL();
+  }
+  return o;
+}
+
 // k, v [B, Hkv, S, 128] may be strided views (last dim dense, 16-byte
 // aligned rows): the decode step's K/V are slices of the QKV GEMM output
 void check_new_rows(const torch::Tensor& t, const char* name) {
@@ -692,6 +757,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_paged", &attn_decode_paged,
         "flash-decode over a paged KV cache: pool [P,Hkv,64,128], block "
         "table int32 [B,pages], lengths int32 [B] (0 = output 0)");
+  m.def("attn_append_paged", &attn_append_paged,
+        "append attention over a paged KV cache: q [B,H,Sq,128], pool "
+        "[P,Hkv,64,128], block table int32 [B,pages], pos int32 [B] "
+        "(pos < 0 = output 0)");
   m.def("kv_page_write", &kv_page_write,
         "scatter new K/V rows [B,Hkv,S,128] into the page pool at "
         "pos[b].. through the block table (pos < 0 skips the sequence)");

@@ -608,8 +608,8 @@ def kv_page_gather(pages, table_row, n):
     """The first ``n`` rows of one sequence as a contiguous
     [1, Hkv, n, 128] tensor. pages: [num_pages, Hkv, 64, 128];
     table_row: the sequence's block-table row (int tensor on the pool's
-    device). Plain torch indexing on both devices — the cold path (later
-    prefill chunks on a paged cache), not a kernel."""
+    device). Plain torch indexing on both devices, not a kernel: a
+    utility for tests and the CPU reference paths, on no model path."""
     npg = (n + PAGE_ROWS - 1) // PAGE_ROWS
     idx = table_row[:npg].to(device=pages.device, dtype=torch.long)
     g = pages[idx]                                  # [npg, Hkv, 64, 128]
@@ -652,6 +652,56 @@ def attn_decode_paged(q, k_pages, v_pages, block_table, lengths, scale,
             kv_page_gather(v_pages, block_table[b], n), scale,
             causal=False))
     return torch.cat(outs, 0)
+
+
+def attn_append_paged(q, k_pages, v_pages, block_table, pos, scale,
+                      max_len=None):
+    """Append attention over a paged KV cache: Sq new query rows per
+    sequence at offset ``pos`` against the rows the sequence owns in the
+    pool, which already hold the new rows at pos .. pos+Sq-1 (written by
+    kv_page_write). Query row i of sequence b attends to rows
+    0 .. pos[b]+i, found through the block table. The shape of every
+    prefill chunk after the first on a PagedKVCache; inference only.
+
+    q: [B, H, Sq, 128] bf16; k_pages/v_pages: [num_pages, Hkv, 64, 128]
+    bf16; block_table: int32 [B, pages_per_seq], entry [b, j] = pool page
+    of rows 64j..64j+63 (only entries j < ceil((pos[b]+Sq)/64) are read;
+    on GPU an entry that is negative or outside the pool contributes no
+    key). ``pos``: a Python int, a list, or an int tensor [B];
+    pos[b] < 0 marks a sequence that takes no part — no table entry is
+    read and its output rows are zero.
+    ``max_len`` bounds max(pos)+Sq and only sizes the split count;
+    None computes it, which costs a host read only when ``pos`` is a
+    device tensor — pass the cache capacity there to stay capturable.
+    GPU -> append_paged.hip; CPU -> gather through the table +
+    attn_append_ref.
+    """
+    B, Sq = q.size(0), q.size(2)
+    if not q.is_cuda:
+        outs = []
+        for b, p in enumerate(_pos_list(pos, B)):
+            if p < 0:
+                outs.append(torch.zeros_like(q[b:b + 1]))
+                continue
+            outs.append(attn_append_ref(
+                q[b:b + 1], kv_page_gather(k_pages, block_table[b], p + Sq),
+                kv_page_gather(v_pages, block_table[b], p + Sq), p, scale))
+        return torch.cat(outs, 0)
+    if torch.is_tensor(pos):
+        if max_len is None:
+            max_len = int(pos.max().item()) + Sq
+        pos_t = pos.to(device=q.device, dtype=torch.int32).contiguous()
+    elif isinstance(pos, int):
+        if max_len is None:
+            max_len = pos + Sq
+        pos_t = torch.full((B,), pos, dtype=torch.int32, device=q.device)
+    else:
+        pos_l = _pos_list(pos, B)
+        if max_len is None:
+            max_len = max(pos_l) + Sq
+        pos_t = torch.tensor(pos_l, dtype=torch.int32, device=q.device)
+    return hip_ext().attn_append_paged(q.contiguous(), k_pages, v_pages,
+                                       block_table, pos_t, max_len, scale)
 
 
 def _rows16(t):
