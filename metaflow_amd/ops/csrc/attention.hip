@@ -10,15 +10,23 @@
 // of the wave's operand held in registers. Consequences:
 //  * softmax statistics are per-lane scalars: the online softmax is a
 //    serial max/sum over the lane's 16 C registers per 32-row sub-tile
-//    plus one shfl_xor(32) — no cross-lane group reductions, no LDS
-//    round-trip for P;
-//  * P / dS become an operand of the second GEMM in-register: the A
-//    operand in fwd and dq (col_to_afrags: packed bf16 pairs + one
-//    shfl_xor(32) exchange), the B operand of the transposed product in
-//    dkdv (acc_to_bfrags: the pack + a v_permlane32_swap half exchange);
+//    plus one exchange between the lane halves in the register file
+//    (half_pair_max / half_pair_sum) — no cross-lane group reductions,
+//    no LDS round-trip for P;
+//  * P / dS are, as they stand, the B operand of the TRANSPOSED second
+//    product (O^T = V^T·P^T, dQ^T = K^T·dS^T, dV^T = dO^T·P, dK^T =
+//    Q^T·dS): acc_to_bfrags packs bf16 pairs and trades halves with
+//    v_permlane32_swap, no ds_bpermute in any tile loop. The results
+//    come out transposed (d in the registers, the row on the lane); each
+//    epilogue turns them back through LDS tiles that are free by then
+//    (store_acc_tile_t, store_acc_tile_t_bf16);
 //  * LDS holds only the streamed operand tiles, in the 16-wide PANEL
-//    layout below, which serves contiguous A-fragment reads and
-//    hardware-transposed B-fragment reads from the same copy.
+//    layout below, which serves contiguous row-fragment reads and
+//    hardware-transposed fragment reads from the same copy;
+//  * one block per (256-row tile, head, batch element) on a 1-D grid,
+//    dispatched heavy causal tiles first (block_coord).
+// col_to_afrags and store_acc_tile (the untransposed forms) remain for
+// the append kernels (col_to_afrags) and the layout probe (both).
 //
 // MFMA 32x32x16 layouts (probed on HW by dbg_mfma32_kernel; the panel /
 // transposed-read / col_to_afrags chain by dbg_attn_layout_kernel):
@@ -190,11 +198,11 @@ DEV void put_elem(float* p, float x) { *p = x; }
 // at dst[off0]. With ROW_SCALE, row i is first multiplied by the value of
 // `lane_scale` held by the lane whose l32 == i (the swapped structure
 // keeps per-row scalars in the lane that owns the row). Used by the
-// forward and the layout probe; dq and dkdv store the same way but keep
-// the loop open-coded, because routing them through here changed their
-// register allocation (dq 252 -> 254 VGPRs; dkdv sits at the 256 limit).
-// Likewise tr_load_bfrags above serves dq and the probe; the forward and
-// dkdv keep open-coded copies of the same addressing.
+// layout probe; the train kernels accumulate the
+// transposed product and store through store_acc_tile_t /
+// store_acc_tile_t_bf16 below. tr_load_bfrags above serves dq and the
+// probe; the forward and dkdv keep open-coded copies of the same
+// addressing.
 template <bool ROW_SCALE, typename T>
 DEV void store_acc_tile(T* dst, long long off0, int row0, const f16f acc[4],
                         int l32, int hi, float lane_scale = 1.f) {
@@ -211,10 +219,157 @@ DEV void store_acc_tile(T* dst, long long off0, int row0, const f16f acc[4],
   }
 }
 
+// ---- accumulator tile as the next MFMA's B operand ----
+// C tile (column on the lane, rows in the registers) -> the two bf16 B
+// fragments (k-steps of 16 rows) of a product that sums over its rows.
+// Packed pairwise, lane half hi holds rows 16s + {0..3, 8..11} + 4hi of
+// step s; two v_permlane32_swap per step (a register-file half exchange,
+// no LDS) trade the lower half's rows 8..11 for the upper half's rows
+// 4..7, so element j of lane half hi is row 16s + 8hi + j: the NATURAL k
+// order. That keeps every product in the k slot it has in the
+// untransposed form (O = P·V, dQ = dS·K, dV = P^T·dO, dK = dS^T·Q), so the
+// fp32 sums are bit-identical to it; feeding the packed registers
+// unswapped (permuted k order) is also a valid operand but changes the
+// order in which an MFMA adds its 16 products.
+DEV void acc_to_bfrags(const f16f& x, bf16x8* pb) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    unsigned int w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      w[i] = pack_bf2(x[8 * s + 2 * i], x[8 * s + 2 * i + 1]);
+    union {
+      unsigned int w[4];
+      bf16x8 v;
+    } u;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      auto r = __builtin_amdgcn_permlane32_swap(w[i], w[2 + i], false,
+                                                false);
+      u.w[i] = r[0];
+      u.w[2 + i] = r[1];
+    }
+    pb[s] = u.v;
+  }
+}
+
+// max / sum of a value over the two lanes l32 and l32 + 32, in the
+// register file: swapping x with itself leaves the lower half's value in
+// r[0] and the upper half's in r[1] on BOTH lanes, so no select follows.
+DEV float half_pair_max(float x) {
+  const unsigned int u = __float_as_uint(x);
+  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
+DEV float half_pair_sum(float x) {
+  const unsigned int u = __float_as_uint(x);
+  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// Lanes of one wave exchanging data through LDS: the hardware runs a
+// wave's DS instructions in order, but the compiler's per-lane alias
+// analysis may move a read above the partner lane's write unless fenced.
+DEV void lds_wave_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Store a wave's TRANSPOSED accumulators (acc[n][r] = X[row = l32][d =
+// n*32 + c_row(r, hi)], the result of the transposed second product) as
+// 32 bf16 rows of a row-major [rows][128] array, NB 32-column blocks per
+// pass through `tw`, NB * 2 KiB of LDS that only this wave touches.
+// A lane's 4 consecutive registers are 4 consecutive d: one 8-byte write
+// into 16-byte slot (d >> 3) ^ (row & (SLOTS - 1)) of its row; the rows
+// then leave as 16 bytes per lane, NB * 64 contiguous bytes per row.
+// With ROW_SCALE every element is first multiplied by the lane's own
+// `lane_scale` (the lane IS the row here, no broadcast).
+template <int NB, bool ROW_SCALE>
+DEV void store_acc_tile_t_bf16(short* dst, long long off0, short* tw,
+                               const f16f acc[4], int lane,
+                               float lane_scale = 1.f) {
+  constexpr int SLOTS = NB * 4;   // 16-byte slots per row and pass
+  constexpr int ROWLEN = NB * 32;  // shorts per row and pass
+  const int l32 = lane & 31, hi = lane >> 5;
+#pragma unroll
+  for (int p = 0; p < 4 / NB; ++p) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      const int n = p * NB + nb;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        bf16x4 w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          w[j] = f2bf(ROW_SCALE ? acc[n][4 * g + j] * lane_scale
+                                : acc[n][4 * g + j]);
+        const int slot = (nb * 4 + g) ^ (l32 & (SLOTS - 1));
+        *(bf16x4*)(tw + l32 * ROWLEN + slot * 8 + hi * 4) = w;
+      }
+    }
+    lds_wave_fence();
+#pragma unroll
+    for (int i = 0; i < SLOTS / 2; ++i) {
+      const int row = i * (64 / SLOTS) + lane / SLOTS;
+      const int c = lane & (SLOTS - 1);
+      const bf16x8 v = *(const bf16x8*)(tw + row * ROWLEN
+                                        + ((c ^ (row & (SLOTS - 1))) * 8));
+      *(bf16x8*)(dst + off0 + (long long)row * ATT_D + p * ROWLEN + c * 8) =
+          v;
+    }
+    if (p + 1 < 4 / NB) lds_wave_fence();
+  }
+}
+
+// ---- block order ----
+// The three MFMA kernels run on a ONE-dimensional grid of T*H*B blocks
+// (T = S/256 tiles) and take their (tile, h, b) from the block id here.
+// Under the causal mask a block's work grows 16-fold with its tile
+// index, one 512-thread block fills a CU, and blocks go out in id order,
+// dealt round-robin over the 8 XCDs. So the id order decides two things:
+//  * which XCD gets which tiles. With the tile index fastest (the former
+//    (T, H, B) grid) XCD x ran tiles x and x + 8 of every head: 10 units
+//    of work on one XCD, 24 on another;
+//  * how long the tail is: the last blocks dispatched run alone.
+// Order: b slowest, then the tile from heavy to light, h fastest. Every
+// XCD then runs every tile (H % 8 == 0 deals each tile's heads evenly),
+// the heavy tiles go first, and the heads of a GQA group at one tile run
+// at the same time. `rank` counts tiles in dispatch order; each kernel
+// maps it to its heaviest-first tile index. Scalar arithmetic only.
+struct BlockCoord {
+  int rank, h, b;
+};
+
+DEV BlockCoord block_coord(int T, int H) {
+  const int bid = blockIdx.x;
+  const int per_b = T * H;
+  BlockCoord c;
+  c.b = bid / per_b;
+  const int r = bid - c.b * per_b;
+  c.rank = r / H;
+  c.h = r - c.rank * H;
+  return c;
+}
+
 // ============================ FORWARD ======================================
-// Grid (S/256, H, B), 8 waves x 32 q rows; each lane keeps its own q row
-// in registers (8 x bf16x8) and streams 64-row K/V tiles through LDS.
+// One block per (q tile, h, b) in heavy-first order (block_coord), 8 waves
+// x 32 q rows; each lane keeps its own q row in registers (8 x bf16x8)
+// and streams 64-row K/V tiles through LDS.
 // LDS: K and V panel tiles, double-buffered = 2 x 2 x 16 KiB = 64 KiB.
+//
+// Q ROW ON THE LANE, BOTH PRODUCTS. S^T = K·Q^T leaves the lane's q row
+// of scores in its registers (kv on the rows), which is already the
+// B-operand shape of the TRANSPOSED second product O^T(d x q) +=
+// V^T(d x kv) · P^T(kv x q): acc_to_bfrags turns P into B fragments in the
+// register file, and the transposed reads of the V tile supply V^T as
+// the A operand, in the same k slots as O = P·V, so O is bit-identical to
+// that form. The accumulators hold d on the rows and q on the lane: the
+// online-softmax rescale and the final 1/l are multiplies by the lane's
+// own scalar, and nothing in the tile loop crosses lanes through LDS.
+// The epilogue transposes each wave's tile through the (by then free)
+// K/V buffers so O leaves as whole 256-byte rows.
 
 template <int BLOCK>  // BLOCK = 512 (8 waves)
 __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
@@ -230,9 +385,10 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
   __shared__ short kp[2][BKV * ATT_D];
   __shared__ short vp[2][BKV * ATT_D];
 
-  const int qb = blockIdx.x;
-  const int h = blockIdx.y;
-  const int b = blockIdx.z;
+  const BlockCoord bc = block_coord(S / BQ, H);
+  const int qb = S / BQ - 1 - bc.rank;  // most kv tiles first
+  const int h = bc.h;
+  const int b = bc.b;
   const int hk = h / (H / Hkv);
   const WaveCoord c = wave_coord();
   const int wid = c.wid, lane = c.lane, l32 = c.l32, hi = c.hi;
@@ -335,7 +491,7 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
         pmax = fmaxf(pmax, sv);
       }
     }
-    pmax = fmaxf(pmax, __shfl_xor(pmax, 32, WAVE));
+    pmax = half_pair_max(pmax);
     const float newm = fmaxf(m_run, pmax);
     const float rescale = __expf(m_run - newm);
     m_run = newm;
@@ -349,26 +505,22 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
         st[t][r] = e;
         psum += e;
       }
-    psum += __shfl_xor(psum, 32, WAVE);
+    psum = half_pair_sum(psum);
     l_run = l_run * rescale + psum;
 
-    // ---- rescale O: the factor for local row c_row(r, hi) is held by
-    // the lanes with l32 == that row; broadcast via shfl ----
-    {
+    // ---- rescale O^T: the lane is the q row, the factor is its own ----
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float f = __shfl(rescale, c_row(r, hi) + 32 * hi, WAVE);
+    for (int n = 0; n < 4; ++n)
 #pragma unroll
-        for (int n = 0; n < 4; ++n) acc_o[n][r] *= f;
-      }
-    }
+      for (int r = 0; r < 16; ++r) acc_o[n][r] *= rescale;
 
-    // ---- P -> bf16 A-fragments via packed pairs + partner exchange ----
-    bf16x8 pa[4];
-    col_to_afrags<2>(st, pa, hi);
+    // ---- P -> bf16 B-fragments in the register file ----
+    bf16x8 pb[4];
+    acc_to_bfrags(st[0], pb);
+    acc_to_bfrags(st[1], pb + 2);
 
-    // ---- PV: O(32q x 128d) += P(32q x 64kv) @ V(64kv x 128d) ----
-    // B-fragments via hardware transpose: same addressing as
+    // ---- PV: O^T(128d x 32q) += V^T(128d x 64kv) @ P^T(64kv x 32q) ----
+    // V^T A-fragments via hardware transpose: same addressing as
     // tr_load_bfrags<BKV> (derivation there), open-coded because the
     // helper form measured 0.6% slower here (3.24 vs 3.22 ms at
     // B=8 H=32 S=4096) with an identical main loop
@@ -389,7 +541,7 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int n = 0; n < 4; ++n)
-          acc_o[n] = mfma32(pa[ks], bfr[n].v, acc_o[n]);
+          acc_o[n] = mfma32(bfr[n].v, pb[ks], acc_o[n]);
       }
     }
     }  // active
@@ -400,9 +552,13 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
 #undef MFX_STAGE_LOAD
 #undef MFX_STAGE_WRITE
 
-  // ---- epilogue: O /= l (row-matched), write bf16 + lse ----
+  // ---- epilogue: O /= l (the lane's own), write bf16 + lse. Every wave
+  // is past the loop's last barrier, so the K/V buffers are free: each
+  // wave transposes its tile through its own 8 KiB of them ----
   float inv_l = 1.f / l_run;
-  store_acc_tile<true>(o, qoff, wid * 32, acc_o, l32, hi, inv_l);
+  short* tw = (wid < 4 ? &kp[0][0] : &vp[0][0]) + (wid & 3) * (32 * ATT_D);
+  store_acc_tile_t_bf16<4, true>(o, qoff + (long long)wid * 32 * ATT_D, tw,
+                                 acc_o, lane, inv_l);
   if (hi == 0)
     lse[hoff + my_qrow] = m_run + __logf(l_run);
 }
@@ -428,12 +584,23 @@ __global__ void attn_bwd_delta_kernel(const short* __restrict__ dout,
 }
 
 // ===================== BACKWARD: dQ ========================================
-// Grid (S/256, H, B), 8 waves x 32 q rows. Swapped structure: lane's
-// C-column is its OWN q row, so lse/delta are per-lane scalars and
-// dS^T -> dS A-fragments use the same col_to_afrags dance. Q and dO rows
-// live in registers. LDS: one K and one V panel tile (2 x 16 KiB =
-// 32 KiB); the K tile serves both S^T (A-fragments) and dS·K
-// (transposed B-fragments).
+// One block per (q tile, h, b) in heavy-first order (block_coord), 8 waves
+// x 32 q rows. Swapped structure: lane's C-column is its OWN q row, so
+// lse/delta are per-lane scalars and dS^T is, as it stands, the B operand
+// of the transposed product dQ^T(d x q) += K^T(d x kv) · dS^T(kv x q)
+// (acc_to_bfrags, natural k order: bit-identical to dQ = dS·K). Q and dO
+// rows live in registers. LDS: K and V panel tiles, double-buffered as in
+// the forward (loads for tile j+1 issue before the MFMAs on tile j, the
+// LDS writes follow them, one barrier per tile): the first pair is the
+// static 2 x 16 KiB, the second pair the 32 KiB of dynamic LDS
+// (DQ_DYN_LDS at the launch site). The K tile serves both S^T
+// (A-fragments, row reads) and the K^T A-fragments (transposed reads).
+// The epilogue transposes each wave's dQ^T tile through its 4 KiB of
+// the static tiles, two 64-column halves.
+
+// dynamic LDS of the dq kernel: its second K/V tile pair, K then V
+extern __shared__ __attribute__((aligned(16))) short dq_kv2[];
+#define DQ_DYN_LDS (2 * 64 * ATT_D * 2)
 
 template <int BLOCK>
 __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
@@ -446,9 +613,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
   __shared__ short kp[BKV * ATT_D];    // K panels
   __shared__ short vp[BKV * ATT_D];    // V panels
 
-  const int qb = blockIdx.x;
-  const int h = blockIdx.y;
-  const int b = blockIdx.z;
+  const BlockCoord bc = block_coord(S / BQ, H);
+  const int qb = S / BQ - 1 - bc.rank;  // most kv tiles first
+  const int h = bc.h;
+  const int b = bc.b;
   const int hk = h / (H / Hkv);
   const int wid = threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -477,15 +645,42 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
 #pragma unroll
   for (int n = 0; n < 4; ++n) acc_dq[n] = (f16f){};
 
+  // per-thread staging slices, 2 x bf16x8 of K and of V per tile; buffer 0
+  // is (kp, vp), buffer 1 the dynamic pair. Macros as in the forward.
+  const int tid = threadIdx.x;
+  bf16x8 stg_k[2], stg_v[2];
+#define MFX_DQ_LOAD(jj)                                                  \
+  {                                                                      \
+    const short* kb_ = k + kvoff0 + (long long)(jj) * BKV * ATT_D;       \
+    const short* vb_ = v + kvoff0 + (long long)(jj) * BKV * ATT_D;       \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                      \
+      const int idx_ = u * BLOCK + tid;                                  \
+      stg_k[u] = *(const bf16x8*)(kb_ + (idx_ / 16) * ATT_D + (idx_ % 16) * 8);\
+      stg_v[u] = *(const bf16x8*)(vb_ + (idx_ / 16) * ATT_D + (idx_ % 16) * 8);\
+    }                                                                    \
+  }
+#define MFX_DQ_WRITE(buf)                                                \
+  {                                                                      \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                      \
+      const int idx_ = u * BLOCK + tid;                                  \
+      const int pel_ = ((idx_ % 16) >> 1) * (BKV * 16) + (idx_ / 16) * 16\
+                       + ((idx_ % 16) & 1) * 8;                          \
+      *(bf16x8*)(((buf) ? dq_kv2 : kp) + pel_) = stg_k[u];               \
+      *(bf16x8*)(((buf) ? dq_kv2 + BKV * ATT_D : vp) + pel_) = stg_v[u]; \
+    }                                                                    \
+  }
   const int kv_tiles = causal ? (qb * BQ + BQ) / BKV : S / BKV;
+  MFX_DQ_LOAD(0);
+  MFX_DQ_WRITE(0);
+  __syncthreads();
   for (int j = 0; j < kv_tiles; ++j) {
-    __syncthreads();
-    stage_panel<BKV, BLOCK>(kp, k + kvoff0 + (long long)j * BKV * ATT_D,
-                            ATT_D);
-    stage_panel<BKV, BLOCK>(vp, v + kvoff0 + (long long)j * BKV * ATT_D,
-                            ATT_D);
-    __syncthreads();
-    if (causal && j * BKV > qb * BQ + wid * 32 + 31) continue;
+    const int cur = j & 1;
+    const short* kpc = cur ? dq_kv2 : kp;
+    const short* vpc = cur ? dq_kv2 + BKV * ATT_D : vp;
+    if (j + 1 < kv_tiles) MFX_DQ_LOAD(j + 1);  // issue loads early
+    // wave-uniform skip of tiles above this wave's rows; staging and the
+    // barrier still run below
+    if (!(causal && j * BKV > qb * BQ + wid * 32 + 31)) {
 
     // per 32-kv sub-tile: S^T, dP^T, dS, dQ — keeps live regs low
 #pragma unroll
@@ -493,8 +688,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
       f16f st = (f16f){}, dpt = (f16f){};
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        bf16x8 kf = frag8_panel<BKV>(kp, t * 32 + l32, s * 16 + hi * 8);
-        bf16x8 vf = frag8_panel<BKV>(vp, t * 32 + l32, s * 16 + hi * 8);
+        bf16x8 kf = frag8_panel<BKV>(kpc, t * 32 + l32, s * 16 + hi * 8);
+        bf16x8 vf = frag8_panel<BKV>(vpc, t * 32 + l32, s * 16 + hi * 8);
         st = mfma32(kf, q_reg[s], st);
         dpt = mfma32(vf, do_reg[s], dpt);
       }
@@ -507,40 +702,37 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
           p = __expf(st[r] * scale - my_lse);
         st[r] = p * (dpt[r] - my_del) * scale;
       }
-      // dQ(32q x 128d) += dS(32q x 32kv) @ K(32kv x 128d)
-      bf16x8 pa[2];
-      col_to_afrags<1>(&st, pa, hi);
+      // dQ^T(128d x 32q) += K^T(128d x 32kv) @ dS^T(32kv x 32q)
+      bf16x8 pb[2];
+      acc_to_bfrags(st, pb);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         BFrag bfr[4];
-        tr_load_bfrags<BKV>(bfr, kp, t * 32 + ks * 16, lane, hi);
+        tr_load_bfrags<BKV>(bfr, kpc, t * 32 + ks * 16, lane, hi);
         asm volatile("s_waitcnt lgkmcnt(0)");
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int n = 0; n < 4; ++n)
-          acc_dq[n] = mfma32(pa[ks], bfr[n].v, acc_dq[n]);
+          acc_dq[n] = mfma32(bfr[n].v, pb[ks], acc_dq[n]);
       }
     }
+    }  // active
+    if (j + 1 < kv_tiles) MFX_DQ_WRITE(cur ^ 1);
+    __syncthreads();
   }
+#undef MFX_DQ_LOAD
+#undef MFX_DQ_WRITE
 
-  // epilogue: C row = q local, col = d. Open-coded, with the row formula
-  // written out: store_acc_tile moves this kernel from 252 to 254 VGPRs,
-  // and c_row() here keeps the compiler from narrowing the row offset
-  // to 32 bits (25 more instructions, measurably slower).
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row_local = (r & 3) + 8 * (r >> 2) + 4 * hi;
-    const long long obase =
-        qoff + (long long)(wid * 32 + row_local) * ATT_D;
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-      dq[obase + n * 32 + l32] = f2bf(acc_dq[n][r]);
-  }
+  // epilogue: C row = d, col = q local; every wave is past the loop's last
+  // barrier, so the static tiles are free for the transpose.
+  short* tw = (wid < 4 ? kp : vp) + (wid & 3) * (32 * 64);
+  store_acc_tile_t_bf16<2, false>(dq, qoff + (long long)wid * 32 * ATT_D,
+                                  tw, acc_dq, lane);
 }
 
 // ===================== BACKWARD: dK/dV =====================================
-// Grid (S/256, H, B) — one Q-HEAD per block, mirroring the dq kernel's
-// structure (which measures 2.2x more TF/s than the round-1 dkdv that
+// One block per (kv tile, h, b) in heavy-first order (block_coord) — one
+// Q-HEAD per block, mirroring the dq kernel's structure (which measures 2.2x more TF/s than the round-1 dkdv that
 // looped all G q-heads inside a (S/256, Hkv, B) grid: 4x fewer blocks
 // with a skewed causal trapezoid starved/imbalanced the chip). Each
 // block accumulates its head's (dK, dV) contribution in registers and
@@ -577,47 +769,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
 // Code generation here is fragile (register limit): the coordinates, the
 // transposed-read addressing and the epilogue stay open-coded rather than
 // going through wave_coord() / tr_load_bfrags / store_acc_tile.
-
-// C tile (column on the lane, rows in the registers) -> the two bf16 B
-// fragments (k-steps of 16 rows) of a product that sums over its rows.
-// Packed pairwise, lane half hi holds rows 16s + {0..3, 8..11} + 4hi of
-// step s; two v_permlane32_swap per step (a register-file half exchange,
-// no LDS) trade the lower half's rows 8..11 for the upper half's rows
-// 4..7, so element j of lane half hi is row 16s + 8hi + j: the NATURAL k
-// order. That keeps every product in the k slot it has in dV = P^T·dO /
-// dK = dS^T·Q, so the fp32 sums are bit-identical to that form; feeding
-// the packed registers unswapped (permuted k order) is also a valid
-// operand but changes the order in which an MFMA adds its 16 products.
-DEV void acc_to_bfrags(const f16f& x, bf16x8* pb) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    unsigned int w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      w[i] = pack_bf2(x[8 * s + 2 * i], x[8 * s + 2 * i + 1]);
-    union {
-      unsigned int w[4];
-      bf16x8 v;
-    } u;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      auto r = __builtin_amdgcn_permlane32_swap(w[i], w[2 + i], false,
-                                                false);
-      u.w[i] = r[0];
-      u.w[2 + i] = r[1];
-    }
-    pb[s] = u.v;
-  }
-}
-
-// Lanes of one wave exchanging data through LDS: the hardware runs a
-// wave's DS instructions in order, but the compiler's per-lane alias
-// analysis may move a read above the partner lane's write unless fenced.
-DEV void lds_wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Store a wave's transposed accumulators (acc[n][r] = X[kv = l32][d =
 // n*32 + c_row(r, hi)]) as 32 rows of a row-major [rows][128] fp32 array:
@@ -662,9 +813,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
   __shared__ float lse_s[BQ2];
   __shared__ float del_s[BQ2];
 
-  const int kvb = blockIdx.x;
-  const int h = blockIdx.y;           // q head
-  const int b = blockIdx.z;
+  const BlockCoord bc = block_coord(S / BKVB, H);
+  const int kvb = bc.rank;            // most q tiles first
+  const int h = bc.h;                 // q head
+  const int b = bc.b;
   const int G = H / Hkv;
   const int hk = h / G;               // kv head this block feeds
   const int wid = threadIdx.x / WAVE;

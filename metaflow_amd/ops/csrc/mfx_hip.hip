@@ -332,8 +332,9 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
   TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, H, S}, q.options().dtype(torch::kFloat32));
-  // v2: 8-wave 32x32 swapped-QK^T structure
-  dim3 grid(S / 256, H, B);
+  // v2: 8-wave 32x32 swapped-QK^T structure; one block per (q tile, h,
+  // b) on a 1-D grid, the kernel maps the block id heavy tiles first
+  dim3 grid((S / 256) * H * B);
   attn_fwd_v2_kernel<512><<<grid, 512, 0, cur_stream()>>>(
       bf(q), bf(k), bf(v), bfm(o), lse.data_ptr<float>(), B, H, Hkv, S,
       (float)scale, causal ? 1 : 0);
@@ -371,7 +372,9 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
   auto dk_part = torch::empty({B, H, S, 128}, f32opts);
   auto dv_part = torch::empty({B, H, S, 128}, f32opts);
   const int icausal = causal ? 1 : 0;
-  const dim3 grid(S / 256, H, B);
+  // one block per (tile, h, b) on a 1-D grid: dkdv and dq map the block
+  // id heavy tiles first (block_coord in attention.hip)
+  const dim3 grid((S / 256) * H * B);
 
   {
     const long long rows = (long long)B * H * S;
@@ -382,8 +385,9 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
     HIP_CHECK_KERNEL();
   }
   {
-    // static 33280 B + the 64 KiB V image exceed the 64 KiB a kernel gets
-    // without asking; the attribute is per device
+    // dkdv: static 33280 B + the 64 KiB V image exceed the 64 KiB a
+    // kernel gets without asking; dq: static 32 KiB + its second K/V
+    // buffer reach it. The attribute is per device.
     static bool lds_set[64] = {};
     int dev_id = 0;
     TORCH_CHECK(hipGetDevice(&dev_id) == hipSuccess && dev_id < 64,
@@ -392,6 +396,10 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
       hipError_t e = hipFuncSetAttribute(
           reinterpret_cast<const void*>(&attn_bwd_dkdv_v2_kernel<512>),
           hipFuncAttributeMaxDynamicSharedMemorySize, DKDV_DYN_LDS);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(
+            reinterpret_cast<const void*>(&attn_bwd_dq_v2_kernel<512>),
+            hipFuncAttributeMaxDynamicSharedMemorySize, DQ_DYN_LDS);
       TORCH_CHECK(e == hipSuccess, "attn_bwd: cannot raise dynamic LDS: ",
                   hipGetErrorString(e));
       lds_set[dev_id] = true;
@@ -412,7 +420,7 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
         bfm(dv), n4_kv, H / Hkv, head_elems);
     HIP_CHECK_KERNEL();
   }
-  attn_bwd_dq_v2_kernel<512><<<grid, 512, 0, cur_stream()>>>(
+  attn_bwd_dq_v2_kernel<512><<<grid, 512, DQ_DYN_LDS, cur_stream()>>>(
       bf(q), bf(k), bf(v), bf(dout), lse.data_ptr<float>(),
       delta.data_ptr<float>(), bfm(dq), B, H, Hkv, S, (float)scale,
       icausal);
