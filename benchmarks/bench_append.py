@@ -16,8 +16,8 @@ length: both are bound by that stream. Needs a GPU: a CPU timing says
 nothing about the kernel.
 
 A second JSON line per shape covers the paged cache
-(K.attn_append_paged, ops/csrc/append_paged.hip) on the same rows held in
-a page pool: pages in order, pages randomly permuted, and the path the
+(K.attn_append_paged, the paged instantiation of ops/csrc/append.hip) on
+the same rows held in a page pool: pages in order, pages randomly permuted, and the path the
 paged engine took before that kernel existed (K.kv_page_gather of K and
 of V, then K.attn_append on the copies), each next to the dense kernel.
 All of them alternate within each of the three runs.

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Paged decode: K.attn_decode_paged (ops/csrc/paged.hip) against
-K.attn_decode_varlen (decode.hip) on identical cache contents, same
-device. The two kernels share their structure; the comparison isolates
-the block-table indirection and the page-aligned split.
+"""Paged decode: K.attn_decode_paged against K.attn_decode_varlen (the
+paged and the dense instantiation of ops/csrc/decode.hip) on identical
+cache contents, same device. The two kernels are one body; the comparison
+isolates the block-table indirection and the page-aligned split.
 
     python benchmarks/bench_paged.py [--iters 50] [--warmup 5]
 

@@ -327,7 +327,7 @@ def paged_cached_attention(q, k, v, view, layer_idx, scale):
     the flash prefill on the fresh tensors; a one-token step is the paged
     decode kernel; a later chunk is the paged append kernel, which reads
     the slot's pages in place through the block table
-    (append_paged.hip)."""
+    (append.hip, paged instantiation)."""
     pc, slot, pos = view.paged, view.slot, view.pos
     S = q.size(2)
     assert q.size(0) == 1, "a paged slot view holds one sequence"

@@ -1,5 +1,7 @@
 // Flash-decode for gfx950: one query row per (b, h) against the KV
-// cache, split-K across the cache length.
+// cache, split-K across the cache length. One kernel body,
+// attn_decode_impl, serves the dense cache (attn_decode_partial_kernel)
+// and the paged one (attn_decode_paged_partial_kernel).
 //
 // Decode is MEMORY-bound (stream L x 128 x 2 tensors of bf16 per head);
 // the design maximizes streaming bandwidth and chip fill, not MFMA:
@@ -15,26 +17,41 @@
 //  * per-wave partials merge through LDS, per-split partials (o, m, l)
 //    merge in a tiny second kernel (attn_decode_merge_kernel).
 //
-// The cache tensors keep their FULL allocation stride (Lmax): no
-// slicing copies; L marks the valid prefix.
+// Dense: the cache tensors keep their FULL allocation stride (Lmax), no
+// slicing copies; L marks the valid prefix, and a split is
+// ceil(L / splits) rows.
+// PAGED (layout in paged.hip): a wave tile is exactly one page, so its
+// base comes from one block-table lookup, wave-uniform. Split chunks are
+// WHOLE pages, computed on the device from lengths[b], so every wave tile
+// starts on a page boundary; an unset or out-of-pool entry contributes
+// nothing and is never dereferenced.
+//
+// Include AFTER paged.hip.
 
 #include "common.h"
 
 #define DEC_D 128
 
-// partial per (split, b, h): o [splits,B,H,128] fp32, ml [splits,B,H,2]
-__global__ __launch_bounds__(256) void attn_decode_partial_kernel(
-    const short* __restrict__ q,    // [B, H, 1, 128]
-    const short* __restrict__ kc,   // [B, Hkv, Lmax, 128]
-    const short* __restrict__ vc,
-    const int* __restrict__ lengths,  // [B] valid prefix per sequence
-    float* __restrict__ o_part, float* __restrict__ ml_part,
-    int B, int H, int Hkv, int Lmax, int splits, float scale) {
+static_assert(DEC_D == PG_D, "head dim of the pool");
+static_assert(WAVE == PG_ROWS, "one wave tile must be one page");
+
+// The one kernel body. Dense: kc/vc [B,Hkv,Lmax,128], table null,
+// num_pages and table_stride unused. PAGED: kc/vc are the pool
+// [num_pages,Hkv,64,128], table int32 [B,table_stride], Lmax unused.
+// Partial per (split, b, h): o [splits,B,H,128] fp32, ml [splits,B,H,2].
+template <bool PAGED>
+DEV void attn_decode_impl(
+    const short* __restrict__ q, const short* __restrict__ kc,
+    const short* __restrict__ vc, const int* __restrict__ table,
+    const int* __restrict__ lengths, float* __restrict__ o_part,
+    float* __restrict__ ml_part, int B, int H, int Hkv, int Lmax,
+    int num_pages, int table_stride, int splits, float scale) {
   const int sp = blockIdx.x;
   const int h = blockIdx.y;
   const int b = blockIdx.z;
   const int hk = h / (H / Hkv);
-  const int L = lengths[b];
+  // paged: a length can never exceed what the table row addresses
+  const int L = PAGED ? min(lengths[b], table_stride * PG_ROWS) : lengths[b];
   const int wid = threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
 
@@ -48,21 +65,43 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(
                               + threadIdx.x]);
   __syncthreads();
 
-  const int chunk = (L + splits - 1) / splits;
-  const int r0 = sp * chunk;
-  const int r1 = min(L, r0 + chunk);
-  const long long kvoff = ((long long)b * Hkv + hk) * Lmax * DEC_D;
+  // This split is units [u0, u1) of the sequence, a unit being one row
+  // (dense) or one whole page (paged: chunk in pages =
+  // ceil(ceil(L/64) / splits), 0 units when L <= 0), and rows >= row_end
+  // are not valid.
+  constexpr int UNIT = PAGED ? PG_ROWS : 1;
+  const int n_units = (L + UNIT - 1) / UNIT;
+  const int chunk = (n_units + splits - 1) / splits;
+  const int u0 = sp * chunk;
+  const int u1 = min(n_units, u0 + chunk);
+  const int row_end = PAGED ? L : u1;
+  const int* trow = PAGED ? table + (long long)b * table_stride : nullptr;
 
   float m_run = -INFINITY, l_run = 0.f;
   float o_acc[2] = {0.f, 0.f};  // lane owns d = 2*lane, 2*lane+1
 
-  for (int base = r0 + wid * WAVE; base < r1; base += 4 * WAVE) {
-    const int row = base + lane;
-    const bool valid = row < r1;
+  // a wave tile is 64 rows: WAVE / UNIT units
+  for (int u = u0 + wid * (WAVE / UNIT); u < u1; u += 4 * (WAVE / UNIT)) {
+    int page = 0;
+    if constexpr (PAGED) {
+      // one lookup per tile, wave-uniform (scalar register)
+      page = __builtin_amdgcn_readfirstlane(trow[u]);
+      // an unset or out-of-pool entry contributes nothing (and is never
+      // dereferenced)
+      if (page < 0 || page >= num_pages) continue;
+    }
+    // the tile's rows are [row0, row0 + 64) of the slab at kvoff: the
+    // page, or the (b, kv head) slab of the dense cache
+    const long long kvoff =
+        PAGED ? ((long long)page * Hkv + hk) * (PG_ROWS * DEC_D)
+              : ((long long)b * Hkv + hk) * Lmax * DEC_D;
+    const int base = u * UNIT;
+    const int row0 = PAGED ? 0 : base;
+    const bool valid = base + lane < row_end;
     // score: dot(q, K[row]) — vec8 streaming loads
     float s = -INFINITY;
     if (valid) {
-      const short* krow = kc + kvoff + (long long)row * DEC_D;
+      const short* krow = kc + kvoff + (long long)(row0 + lane) * DEC_D;
       float acc = 0.f;
 #pragma unroll
       for (int d8 = 0; d8 < DEC_D / 8; ++d8) {
@@ -81,11 +120,11 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(
     o_acc[1] *= rescale;
     m_run = m_new;
     // V accumulate: lane owns 2 d-columns; p_r broadcast per row
-    const int nrows = min(WAVE, r1 - base);
+    const int nrows = min(WAVE, row_end - base);
     for (int r = 0; r < nrows; ++r) {
       const float pr = __shfl(p, r, WAVE);
       if (pr != 0.f) {
-        const short* vrow = vc + kvoff + (long long)(base + r) * DEC_D;
+        const short* vrow = vc + kvoff + (long long)(row0 + r) * DEC_D;
         o_acc[0] += pr * bf2f(vrow[2 * lane]);
         o_acc[1] += pr * bf2f(vrow[2 * lane + 1]);
       }
@@ -114,6 +153,7 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(
       o0 += f * red_o[w][2 * lane];
       o1 += f * red_o[w][2 * lane + 1];
     }
+    // empty splits (and length-0 sequences) write m = -inf, l = 0, o = 0
     const long long po =
         (((long long)sp * B + b) * H + h) * DEC_D;
     o_part[po + 2 * lane] = o0;
@@ -124,6 +164,30 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(
       ml_part[pm + 1] = l_blk;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void attn_decode_partial_kernel(
+    const short* __restrict__ q,    // [B, H, 1, 128]
+    const short* __restrict__ kc,   // [B, Hkv, Lmax, 128]
+    const short* __restrict__ vc,
+    const int* __restrict__ lengths,  // [B] valid prefix per sequence
+    float* __restrict__ o_part, float* __restrict__ ml_part,
+    int B, int H, int Hkv, int Lmax, int splits, float scale) {
+  attn_decode_impl<false>(q, kc, vc, nullptr, lengths, o_part, ml_part, B, H,
+                          Hkv, Lmax, 0, 0, splits, scale);
+}
+
+__global__ __launch_bounds__(256) void attn_decode_paged_partial_kernel(
+    const short* __restrict__ q,        // [B, H, 1, 128]
+    const short* __restrict__ kp,       // [num_pages, Hkv, 64, 128]
+    const short* __restrict__ vp,
+    const int* __restrict__ table,      // [B, table_stride]
+    const int* __restrict__ lengths,    // [B] valid rows per sequence
+    float* __restrict__ o_part, float* __restrict__ ml_part,
+    int B, int H, int Hkv, int num_pages, int table_stride, int splits,
+    float scale) {
+  attn_decode_impl<true>(q, kp, vp, table, lengths, o_part, ml_part, B, H,
+                         Hkv, 0, num_pages, table_stride, splits, scale);
 }
 
 // merge the split partials: one wave per (b, h), lane owns 2 d-columns

@@ -11,10 +11,9 @@
 #include "adam.hip"
 #include "cross_entropy.hip"
 #include "attention.hip"
-#include "append.hip"
-#include "decode.hip"
 #include "paged.hip"
-#include "append_paged.hip"
+#include "decode.hip"
+#include "append.hip"
 #include "debug_kernels.hip"
 
 namespace {
@@ -429,6 +428,52 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
 }
 
 // ---------------------------------------------------------- flash-decode
+// The int32 [B] device vectors (lengths, pos) that the cached-attention
+// kernels read and the host never does.
+void check_int32_vec(const torch::Tensor& t, int B, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
+              t.numel() == B && t.is_contiguous(),
+              name, " must be int32 [B] on GPU");
+}
+
+// enough splits to fill 256 CUs at small B*H, chunks >= ~256 rows
+int decode_splits(int B, int H, long max_len) {
+  int splits = (int)std::max<long>(1, 1024 / ((long)B * H));
+  splits = (int)std::min<long>(splits, (max_len + 255) / 256);
+  return std::max(splits, 1);
+}
+
+// Partials, the dense (table == nullptr: kc/vc [B,Hkv,Lmax,128]) or the
+// paged (kc/vc the pool) instantiation of decode.hip, and the merge.
+torch::Tensor decode_launch(torch::Tensor& q, const torch::Tensor& kc,
+                            const torch::Tensor& vc, const int* table,
+                            const torch::Tensor& lengths, int Hkv, int Lmax,
+                            int num_pages, int table_stride, int splits,
+                            double scale) {
+  const int B = q.size(0), H = q.size(1);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto o_part = torch::empty({splits, B, H, 128}, f32);
+  auto ml_part = torch::empty({splits, B, H, 2}, f32);
+  auto o = torch::empty_like(q);
+  dim3 grid(splits, H, B);
+  if (table)
+    attn_decode_paged_partial_kernel<<<grid, 256, 0, cur_stream()>>>(
+        bf(q), bf(kc), bf(vc), table, lengths.data_ptr<int>(),
+        o_part.data_ptr<float>(), ml_part.data_ptr<float>(), B, H, Hkv,
+        num_pages, table_stride, splits, (float)scale);
+  else
+    attn_decode_partial_kernel<<<grid, 256, 0, cur_stream()>>>(
+        bf(q), bf(kc), bf(vc), lengths.data_ptr<int>(),
+        o_part.data_ptr<float>(), ml_part.data_ptr<float>(), B, H, Hkv,
+        Lmax, splits, (float)scale);
+  HIP_CHECK_KERNEL();
+  attn_decode_merge_kernel<<<B * H, 64, 0, cur_stream()>>>(
+      o_part.data_ptr<float>(), ml_part.data_ptr<float>(), bfm(o), B, H,
+      splits);
+  HIP_CHECK_KERNEL();
+  return o;
+}
+
 torch::Tensor attn_decode_varlen(torch::Tensor q, torch::Tensor kc,
                                  torch::Tensor vc, torch::Tensor lengths,
                                  long max_len, double scale) {
@@ -441,28 +486,9 @@ torch::Tensor attn_decode_varlen(torch::Tensor q, torch::Tensor kc,
               "decode expects q [B,H,1,128]");
   TORCH_CHECK(kc.size(3) == 128 && max_len >= 1 && max_len <= Lmax);
   TORCH_CHECK(H % Hkv == 0);
-  TORCH_CHECK(lengths.is_cuda() &&
-              lengths.scalar_type() == torch::kInt32 &&
-              lengths.numel() == B, "lengths must be int32 [B] on GPU");
-  // enough splits to fill 256 CUs at small B*H, chunks >= ~256 rows
-  int splits = (int)std::max<long>(1, 1024 / ((long)B * H));
-  splits = (int)std::min<long>(splits, (max_len + 255) / 256);
-  splits = std::max(splits, 1);
-  auto f32 = q.options().dtype(torch::kFloat32);
-  auto o_part = torch::empty({splits, B, H, 128}, f32);
-  auto ml_part = torch::empty({splits, B, H, 2}, f32);
-  auto o = torch::empty_like(q);
-  dim3 grid(splits, H, B);
-  attn_decode_partial_kernel<<<grid, 256, 0, cur_stream()>>>(
-      bf(q), bf(kc), bf(vc), lengths.data_ptr<int>(),
-      o_part.data_ptr<float>(), ml_part.data_ptr<float>(), B, H, Hkv,
-      Lmax, splits, (float)scale);
-  HIP_CHECK_KERNEL();
-  attn_decode_merge_kernel<<<B * H, 64, 0, cur_stream()>>>(
-      o_part.data_ptr<float>(), ml_part.data_ptr<float>(), bfm(o), B, H,
-      splits);
-  HIP_CHECK_KERNEL();
-  return o;
+  check_int32_vec(lengths, B, "lengths");
+  return decode_launch(q, kc, vc, nullptr, lengths, Hkv, Lmax, 0, 0,
+                       decode_splits(B, H, max_len), scale);
 }
 
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc,
@@ -476,26 +502,14 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc,
 // Sq new query rows per sequence at device-side offsets pos[b], against
 // the cache rows 0 .. pos[b]+Sq-1 (append.hip). max_len bounds
 // max(pos) + Sq and only sizes the split count: pos is never read here.
-torch::Tensor attn_append(torch::Tensor q, torch::Tensor kc,
-                          torch::Tensor vc, torch::Tensor pos,
-                          long max_len, double scale) {
-  check_bf16(q, "q");
-  check_bf16(kc, "kc");
-  check_bf16(vc, "vc");
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128 && q.size(2) >= 1,
-              "append expects q [B,H,Sq,128]");
-  const int B = q.size(0), H = q.size(1), Sq = q.size(2);
-  TORCH_CHECK(kc.dim() == 4 && kc.size(0) == B && kc.size(3) == 128,
-              "append expects k_cache [B,Hkv,Lmax,128]");
-  TORCH_CHECK(vc.sizes() == kc.sizes(),
-              "k_cache and v_cache must have the same shape");
-  const int Hkv = kc.size(1), Lmax = kc.size(2);
-  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
-  TORCH_CHECK(max_len >= 1 && max_len <= Lmax,
-              "max_len must be in [1, Lmax]");
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
-              pos.numel() == B && pos.is_contiguous(),
-              "pos must be int32 [B] on GPU");
+// The dense and the paged call share the launch plan and the launch.
+struct AppendPlan {
+  bool small;  // block of 1 wave, else 4
+  int q_tiles;
+  int splits;
+};
+
+AppendPlan append_plan(int B, int H, int Sq, long max_len) {
   // one wave (32 query rows) for the verify block, four for a chunk
   const bool small = Sq <= 32;
   const int bq = small ? 32 : 128;
@@ -504,7 +518,20 @@ torch::Tensor attn_append(torch::Tensor q, torch::Tensor kc,
   const long wgs = (long)B * H * q_tiles;
   int splits = (int)std::max<long>(1, (small ? 1024 : 512) / wgs);
   splits = (int)std::min<long>(splits, (max_len + 255) / 256);
-  splits = std::max(splits, 1);
+  return {small, q_tiles, std::max(splits, 1)};
+}
+
+// Partials (with splits > 1), the dense (table == nullptr: kc/vc
+// [B,Hkv,Lmax,128]) or the paged (kc/vc the pool) instantiation of
+// append.hip at the plan's block size, and the merge.
+torch::Tensor append_launch(torch::Tensor& q, const torch::Tensor& kc,
+                            const torch::Tensor& vc, const int* table,
+                            const torch::Tensor& pos, int Hkv, int Lmax,
+                            int num_pages, int table_stride, long max_len,
+                            double scale) {
+  const int B = q.size(0), H = q.size(1), Sq = q.size(2);
+  const AppendPlan plan = append_plan(B, H, Sq, max_len);
+  const int splits = plan.splits;
   auto o = torch::empty_like(q);
   auto f32 = q.options().dtype(torch::kFloat32);
   torch::Tensor o_part, ml_part;
@@ -516,15 +543,23 @@ torch::Tensor attn_append(torch::Tensor q, torch::Tensor kc,
     o_part_p = o_part.data_ptr<float>();
     ml_part_p = ml_part.data_ptr<float>();
   }
-  dim3 grid(q_tiles * splits, H, B);
-  if (small)
-    attn_append_kernel<1><<<grid, 64, 0, cur_stream()>>>(
-        bf(q), bf(kc), bf(vc), pos.data_ptr<int>(), bfm(o), o_part_p,
-        ml_part_p, B, H, Hkv, Sq, Lmax, splits, (float)scale);
+  dim3 grid(plan.q_tiles * splits, H, B);
+  auto launch = [&](auto nw) {
+    constexpr int NW = decltype(nw)::value;
+    if (table)
+      attn_append_paged_kernel<NW><<<grid, NW * WAVE, 0, cur_stream()>>>(
+          bf(q), bf(kc), bf(vc), table, pos.data_ptr<int>(), bfm(o),
+          o_part_p, ml_part_p, B, H, Hkv, Sq, num_pages, table_stride,
+          splits, (float)scale);
+    else
+      attn_append_kernel<NW><<<grid, NW * WAVE, 0, cur_stream()>>>(
+          bf(q), bf(kc), bf(vc), pos.data_ptr<int>(), bfm(o), o_part_p,
+          ml_part_p, B, H, Hkv, Sq, Lmax, splits, (float)scale);
+  };
+  if (plan.small)
+    launch(std::integral_constant<int, 1>{});
   else
-    attn_append_kernel<4><<<grid, 256, 0, cur_stream()>>>(
-        bf(q), bf(kc), bf(vc), pos.data_ptr<int>(), bfm(o), o_part_p,
-        ml_part_p, B, H, Hkv, Sq, Lmax, splits, (float)scale);
+    launch(std::integral_constant<int, 4>{});
   HIP_CHECK_KERNEL();
   if (splits > 1) {
     const long long R = (long long)B * H * Sq;
@@ -533,6 +568,28 @@ torch::Tensor attn_append(torch::Tensor q, torch::Tensor kc,
     HIP_CHECK_KERNEL();
   }
   return o;
+}
+
+torch::Tensor attn_append(torch::Tensor q, torch::Tensor kc,
+                          torch::Tensor vc, torch::Tensor pos,
+                          long max_len, double scale) {
+  check_bf16(q, "q");
+  check_bf16(kc, "kc");
+  check_bf16(vc, "vc");
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128 && q.size(2) >= 1,
+              "append expects q [B,H,Sq,128]");
+  const int B = q.size(0), H = q.size(1);
+  TORCH_CHECK(kc.dim() == 4 && kc.size(0) == B && kc.size(3) == 128,
+              "append expects k_cache [B,Hkv,Lmax,128]");
+  TORCH_CHECK(vc.sizes() == kc.sizes(),
+              "k_cache and v_cache must have the same shape");
+  const int Hkv = kc.size(1), Lmax = kc.size(2);
+  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  TORCH_CHECK(max_len >= 1 && max_len <= Lmax,
+              "max_len must be in [1, Lmax]");
+  check_int32_vec(pos, B, "pos");
+  return append_launch(q, kc, vc, nullptr, pos, Hkv, Lmax, 0, 0, max_len,
+                       scale);
 }
 
 // ------------------------------------------------------- paged KV cache
@@ -571,36 +628,16 @@ torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kp,
   const int table_stride = table.size(1);
   TORCH_CHECK(max_len >= 1 && max_len <= (long)table_stride * PG_ROWS,
               "max_len must be in [1, 64 * pages_per_seq]");
-  TORCH_CHECK(lengths.is_cuda() &&
-              lengths.scalar_type() == torch::kInt32 &&
-              lengths.numel() == B && lengths.is_contiguous(),
-              "lengths must be int32 [B] on GPU");
-  // attn_decode_varlen's split count (fill 256 CUs at small B*H, chunks
-  // >= ~256 rows), capped by the page count: a split is whole pages
-  int splits = (int)std::max<long>(1, 1024 / ((long)B * H));
-  splits = (int)std::min<long>(splits, (max_len + 255) / 256);
-  splits = (int)std::min<long>(splits,
-                               (max_len + PG_ROWS - 1) / PG_ROWS);
-  splits = std::max(splits, 1);
-  auto f32 = q.options().dtype(torch::kFloat32);
-  auto o_part = torch::empty({splits, B, H, 128}, f32);
-  auto ml_part = torch::empty({splits, B, H, 2}, f32);
-  auto o = torch::empty_like(q);
-  dim3 grid(splits, H, B);
-  attn_decode_paged_partial_kernel<<<grid, 256, 0, cur_stream()>>>(
-      bf(q), bf(kp), bf(vp), table.data_ptr<int>(),
-      lengths.data_ptr<int>(), o_part.data_ptr<float>(),
-      ml_part.data_ptr<float>(), B, H, Hkv, num_pages, table_stride,
-      splits, (float)scale);
-  HIP_CHECK_KERNEL();
-  attn_decode_merge_kernel<<<B * H, 64, 0, cur_stream()>>>(
-      o_part.data_ptr<float>(), ml_part.data_ptr<float>(), bfm(o), B, H,
-      splits);
-  HIP_CHECK_KERNEL();
-  return o;
+  check_int32_vec(lengths, B, "lengths");
+  // the dense split count, capped by the page count: a split is whole
+  // pages
+  const int splits = (int)std::min<long>(
+      decode_splits(B, H, max_len), (max_len + PG_ROWS - 1) / PG_ROWS);
+  return decode_launch(q, kp, vp, table.data_ptr<int>(), lengths, Hkv, 0,
+                       num_pages, table_stride, splits, scale);
 }
 
-// Append attention through the block table (append_paged.hip): Sq new
+// Append attention through the block table (append.hip, PAGED): Sq new
 // query rows per sequence at device-side offsets pos[b] (pos[b] < 0 = the
 // sequence takes no part, output 0). max_len bounds max(pos) + Sq and
 // only sizes the split count: neither pos nor the table is read here.
@@ -612,56 +649,16 @@ torch::Tensor attn_append_paged(torch::Tensor q, torch::Tensor kp,
   check_page_pool(kp, vp);
   TORCH_CHECK(q.dim() == 4 && q.size(3) == PG_D && q.size(2) >= 1,
               "paged append expects q [B,H,Sq,128]");
-  const int B = q.size(0), H = q.size(1), Sq = q.size(2);
+  const int B = q.size(0), H = q.size(1);
   const int num_pages = kp.size(0), Hkv = kp.size(1);
   TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
   check_block_table(table, B);
   const int table_stride = table.size(1);
   TORCH_CHECK(max_len >= 1 && max_len <= (long)table_stride * PG_ROWS,
               "max_len must be in [1, 64 * pages_per_seq]");
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
-              pos.numel() == B && pos.is_contiguous(),
-              "pos must be int32 [B] on GPU");
-  // attn_append's launch, verbatim: one wave (32 query rows) for the
-  // verify block, four for a chunk; enough workgroups to fill 256 CUs,
-  // chunks of >= ~256 cache rows
-  const bool small = Sq <= 32;
-  const int bq = small ? 32 : 128;
-  const int q_tiles = (Sq + bq - 1) / bq;
-  const long wgs = (long)B * H * q_tiles;
-  int splits = (int)std::max<long>(1, (small ? 1024 : 512) / wgs);
-  splits = (int)std::min<long>(splits, (max_len + 255) / 256);
-  splits = std::max(splits, 1);
-  auto o = torch::empty_like(q);
-  auto f32 = q.options().dtype(torch::kFloat32);
-  torch::Tensor o_part, ml_part;
-  float* o_part_p = nullptr;
-  float* ml_part_p = nullptr;
-  if (splits > 1) {
-    o_part = torch::empty({splits, B, H, Sq, 128}, f32);
-    ml_part = torch::empty({splits, B, H, Sq, 2}, f32);
-    o_part_p = o_part.data_ptr<float>();
-    ml_part_p = ml_part.data_ptr<float>();
-  }
-  dim3 grid(q_tiles * splits, H, B);
-  if (small)
-    attn_append_paged_kernel<1><<<grid, 64, 0, cur_stream()>>>(
-        bf(q), bf(kp), bf(vp), table.data_ptr<int>(), pos.data_ptr<int>(),
-        bfm(o), o_part_p, ml_part_p, B, H, Hkv, Sq, num_pages,
-        table_stride, splits, (float)scale);
-  else
-    attn_append_paged_kernel<4><<<grid, 256, 0, cur_stream()>>>(
-        bf(q), bf(kp), bf(vp), table.data_ptr<int>(), pos.data_ptr<int>(),
-        bfm(o), o_part_p, ml_part_p, B, H, Hkv, Sq, num_pages,
-        table_stride, splits, (float)scale);
-  HIP_CHECK_KERNEL();
-  if (splits > 1) {
-    const long long R = (long long)B * H * Sq;
-    attn_append_merge_kernel<<<(int)((R + 3) / 4), 256, 0, cur_stream()>>>(
-        o_part_p, ml_part_p, bfm(o), R, splits);
-    HIP_CHECK_KERNEL();
-  }
-  return o;
+  check_int32_vec(pos, B, "pos");
+  return append_launch(q, kp, vp, table.data_ptr<int>(), pos, Hkv, 0,
+                       num_pages, table_stride, max_len, scale);
 }
 
 // k, v [B, Hkv, S, 128] may be strided views (last dim dense, 16-byte
@@ -687,9 +684,7 @@ void kv_page_write(torch::Tensor k, torch::Tensor v, torch::Tensor kp,
   const int B = k.size(0), Hkv = k.size(1), S = k.size(2);
   TORCH_CHECK(kp.size(1) == Hkv, "k and the pool disagree on Hkv");
   check_block_table(table, B);
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
-              pos.numel() == B && pos.is_contiguous(),
-              "pos must be int32 [B] on GPU");
+  check_int32_vec(pos, B, "pos");
   const long long vecs = (long long)B * Hkv * S * (PG_D / 8);
   if (vecs == 0) return;
   kv_page_write_kernel<<<grid_for(vecs), kBlock, 0, cur_stream()>>>(

@@ -483,6 +483,14 @@ def attn_decode(q, k_cache, v_cache, length, scale):
                          v_cache[:, :, :length], scale, causal=False)
 
 
+def _lengths_tensor(lengths, device):
+    """``lengths`` (list or tensor) as the contiguous int32 [B] tensor on
+    ``device`` that the decode kernels read."""
+    if not torch.is_tensor(lengths):
+        lengths = torch.tensor(lengths, dtype=torch.int32, device=device)
+    return lengths.to(device=device, dtype=torch.int32).contiguous()
+
+
 def attn_decode_varlen(q, k_cache, v_cache, lengths, scale,
                        max_len=None):
     """Flash-decode with a per-sequence valid prefix (continuous
@@ -495,10 +503,7 @@ def attn_decode_varlen(q, k_cache, v_cache, lengths, scale,
     chunks from the device lengths, empty splits cost nothing).
     """
     if q.is_cuda:
-        if not torch.is_tensor(lengths):
-            lengths = torch.tensor(lengths, dtype=torch.int32,
-                                   device=q.device)
-        lengths = lengths.to(device=q.device, dtype=torch.int32)
+        lengths = _lengths_tensor(lengths, q.device)
         if max_len is None:
             max_len = int(lengths.max().item())
         return hip_ext().attn_decode_varlen(
@@ -524,6 +529,28 @@ def _pos_list(pos, B):
     pos = [int(p) for p in pos]
     assert len(pos) == B, "pos must hold one offset per sequence"
     return pos
+
+
+def _pos_tensor(pos, q, max_len):
+    """``pos`` (int, list or tensor) as the int32 [B] tensor on q's device
+    that the append kernels read, and ``max_len``, computed as
+    max(pos) + Sq where the caller passed None (a host read only when
+    ``pos`` is a device tensor)."""
+    B, Sq = q.size(0), q.size(2)
+    if torch.is_tensor(pos):
+        if max_len is None:
+            max_len = int(pos.max().item()) + Sq
+        pos_t = pos.to(device=q.device, dtype=torch.int32).contiguous()
+    elif isinstance(pos, int):
+        if max_len is None:
+            max_len = pos + Sq
+        pos_t = torch.full((B,), pos, dtype=torch.int32, device=q.device)
+    else:
+        pos_l = _pos_list(pos, B)
+        if max_len is None:
+            max_len = max(pos_l) + Sq
+        pos_t = torch.tensor(pos_l, dtype=torch.int32, device=q.device)
+    return pos_t, max_len
 
 
 def _append_ref_block(q, k_all, v_all, scale, pos):
@@ -580,20 +607,7 @@ def attn_append(q, k_cache, v_cache, pos, scale, max_len=None):
     """
     if not q.is_cuda:
         return attn_append_ref(q, k_cache, v_cache, pos, scale)
-    B, Sq = q.size(0), q.size(2)
-    if torch.is_tensor(pos):
-        if max_len is None:
-            max_len = int(pos.max().item()) + Sq
-        pos_t = pos.to(device=q.device, dtype=torch.int32).contiguous()
-    elif isinstance(pos, int):
-        if max_len is None:
-            max_len = pos + Sq
-        pos_t = torch.full((B,), pos, dtype=torch.int32, device=q.device)
-    else:
-        pos_l = _pos_list(pos, B)
-        if max_len is None:
-            max_len = max(pos_l) + Sq
-        pos_t = torch.tensor(pos_l, dtype=torch.int32, device=q.device)
+    pos_t, max_len = _pos_tensor(pos, q, max_len)
     return hip_ext().attn_append(q.contiguous(), k_cache, v_cache, pos_t,
                                  max_len, scale)
 
@@ -630,14 +644,11 @@ def attn_decode_paged(q, k_pages, v_pages, block_table, lengths, scale,
     read); lengths: int32 [B] (GPU) or list/IntTensor. ``max_len`` (the
     cache capacity) sizes the split count, so lengths is never read on
     the host and the call is always hipGraph-capturable.
-    GPU -> paged.hip; CPU -> gather through the table + fp32 reference.
+    GPU -> decode.hip (its paged instantiation); CPU -> gather through the
+    table + fp32 reference.
     """
     if q.is_cuda:
-        if not torch.is_tensor(lengths):
-            lengths = torch.tensor(lengths, dtype=torch.int32,
-                                   device=q.device)
-        lengths = lengths.to(device=q.device,
-                             dtype=torch.int32).contiguous()
+        lengths = _lengths_tensor(lengths, q.device)
         return hip_ext().attn_decode_paged(
             q.contiguous(), k_pages, v_pages, block_table, lengths,
             max_len, scale)
@@ -673,8 +684,8 @@ def attn_append_paged(q, k_pages, v_pages, block_table, pos, scale,
     ``max_len`` bounds max(pos)+Sq and only sizes the split count;
     None computes it, which costs a host read only when ``pos`` is a
     device tensor — pass the cache capacity there to stay capturable.
-    GPU -> append_paged.hip; CPU -> gather through the table +
-    attn_append_ref.
+    GPU -> append.hip (its paged instantiation); CPU -> gather through the
+    table + attn_append_ref.
     """
     B, Sq = q.size(0), q.size(2)
     if not q.is_cuda:
@@ -687,19 +698,7 @@ def attn_append_paged(q, k_pages, v_pages, block_table, pos, scale,
                 q[b:b + 1], kv_page_gather(k_pages, block_table[b], p + Sq),
                 kv_page_gather(v_pages, block_table[b], p + Sq), p, scale))
         return torch.cat(outs, 0)
-    if torch.is_tensor(pos):
-        if max_len is None:
-            max_len = int(pos.max().item()) + Sq
-        pos_t = pos.to(device=q.device, dtype=torch.int32).contiguous()
-    elif isinstance(pos, int):
-        if max_len is None:
-            max_len = pos + Sq
-        pos_t = torch.full((B,), pos, dtype=torch.int32, device=q.device)
-    else:
-        pos_l = _pos_list(pos, B)
-        if max_len is None:
-            max_len = max(pos_l) + Sq
-        pos_t = torch.tensor(pos_l, dtype=torch.int32, device=q.device)
+    pos_t, max_len = _pos_tensor(pos, q, max_len)
     return hip_ext().attn_append_paged(q.contiguous(), k_pages, v_pages,
                                        block_table, pos_t, max_len, scale)
 

@@ -8,19 +8,14 @@ instantiation stages its tiles in place and depends on co-resident blocks
 to cover the load latency.
 """
 
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                    "metaflow_amd", "ops", "csrc")
+from .kernel_remarks import hipcc, kernel_usage, resource_usage
 
-# append.hip builds on attention.hip's helpers and is included after it,
-# as in mfx_hip.hip
+# append.hip builds on attention.hip's helpers and paged.hip's constants
+# and is included after them, as in mfx_hip.hip
 TU = """#include "attention.hip"
+#include "paged.hip"
 #include "append.hip"
 template __global__ void attn_append_kernel<1>(
     const short*, const short*, const short*, const int*, short*, float*,
@@ -41,41 +36,11 @@ LDS_BYTES = 2 * 64 * 128 * 2
 OCCUPANCY = 2
 
 
-def _hipcc():
-    return shutil.which("hipcc") or (
-        "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc")
-        else None)
-
-
-@pytest.mark.skipif(_hipcc() is None, reason="hipcc not installed")
+@pytest.mark.skipif(hipcc() is None, reason="hipcc not installed")
 def test_append_kernel_resources(tmp_path):
-    src = tmp_path / "append_tu.hip"
-    src.write_text(TU)
-    proc = subprocess.run(
-        [_hipcc(), "--offload-arch=gfx950", "--cuda-device-only", "-O3",
-         "-std=c++17", "-S", "-Rpass-analysis=kernel-resource-usage",
-         "-I", CSRC, str(src), "-o", str(tmp_path / "append_tu.s")],
-        capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-
-    # remarks come as one block per kernel, headed by "Function Name:"
-    usage = {}
-    cur = None
-    for line in proc.stderr.splitlines():
-        m = re.search(r"remark: (?:Function Name: (\S+)|\s*([^:]+): (\d+))",
-                      line)
-        if not m:
-            continue
-        if m.group(1):
-            cur = usage.setdefault(m.group(1), {})
-        elif cur is not None:
-            cur[m.group(2).strip()] = int(m.group(3))
-
+    usage = resource_usage(TU, tmp_path, "append_tu")
     for frag in KERNELS:
-        names = [n for n in usage if frag in n]
-        assert len(names) == 1, (frag, sorted(usage))
-        u = usage[names[0]]
-        print(frag, u)
+        u = kernel_usage(usage, frag)
         assert u["SGPRs Spill"] == 0, (frag, u)
         assert u["VGPRs Spill"] == 0, (frag, u)
         assert u["ScratchSize [bytes/lane]"] == 0, (frag, u)

@@ -1,5 +1,5 @@
-"""append_paged.hip on the GPU: K.attn_append_paged against the fp32
-reference on the shapes that take each of the kernel's paths, against the
+"""append.hip's paged instantiation on the GPU: K.attn_append_paged
+against the fp32 reference on the shapes that take each of the kernel's paths, against the
 dense append kernel, under hipGraph capture, and the model wiring.
 
 Pool setup as in test_paged_gpu.py: the pool is larger than what the

@@ -19,15 +19,11 @@ loop really contains:
   or scratch memory at all: Q, dO, lse and delta stay in registers.
 """
 
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                    "metaflow_amd", "ops", "csrc")
+from .kernel_remarks import compile_tu, hipcc
 
 TU = """#include "attention.hip"
 template __global__ void attn_fwd_v2_kernel<512>(
@@ -47,25 +43,11 @@ LOOPS = {
 _asm = {}
 
 
-def _hipcc():
-    return shutil.which("hipcc") or (
-        "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc")
-        else None)
-
-
 def _assembly(tmp_path_factory):
     """The translation unit's assembly, compiled once for both cases."""
     if "s" not in _asm:
         tmp = tmp_path_factory.mktemp("fwd_dq_asm")
-        src = tmp / "fwd_dq_tu.hip"
-        src.write_text(TU)
-        out = tmp / "fwd_dq_tu.s"
-        proc = subprocess.run(
-            [_hipcc(), "--offload-arch=gfx950", "--cuda-device-only", "-O3",
-             "-std=c++17", "-S", "-I", CSRC, str(src), "-o", str(out)],
-            capture_output=True, text=True)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        _asm["s"] = out.read_text()
+        _asm["s"], _ = compile_tu(TU, tmp, "fwd_dq_tu")
     return _asm["s"]
 
 
@@ -89,7 +71,7 @@ def _loop_instructions(asm, kernel):
     return ins
 
 
-@pytest.mark.skipif(_hipcc() is None, reason="hipcc not installed")
+@pytest.mark.skipif(hipcc() is None, reason="hipcc not installed")
 @pytest.mark.parametrize("kernel", sorted(LOOPS))
 def test_loop_has_no_lane_exchange_and_no_refetch(kernel, tmp_path_factory):
     mfmas, staging_loads = LOOPS[kernel]

@@ -16,15 +16,11 @@ needed) and counts what the loop really contains:
   K or V re-fetch would add at least 8.
 """
 
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                    "metaflow_amd", "ops", "csrc")
+from .kernel_remarks import compile_tu, hipcc
 
 TU = """#include "attention.hip"
 template __global__ void attn_bwd_dkdv_v2_kernel<512>(
@@ -33,12 +29,6 @@ template __global__ void attn_bwd_dkdv_v2_kernel<512>(
 """
 
 STAGING_LOADS = 5
-
-
-def _hipcc():
-    return shutil.which("hipcc") or (
-        "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc")
-        else None)
 
 
 def _loop_instructions(asm):
@@ -61,17 +51,10 @@ def _loop_instructions(asm):
     return ins
 
 
-@pytest.mark.skipif(_hipcc() is None, reason="hipcc not installed")
+@pytest.mark.skipif(hipcc() is None, reason="hipcc not installed")
 def test_dkdv_loop_has_no_lane_exchange_and_no_kv_refetch(tmp_path):
-    src = tmp_path / "dkdv_tu.hip"
-    src.write_text(TU)
-    out = tmp_path / "dkdv_tu.s"
-    proc = subprocess.run(
-        [_hipcc(), "--offload-arch=gfx950", "--cuda-device-only", "-O3",
-         "-std=c++17", "-S", "-I", CSRC, str(src), "-o", str(out)],
-        capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    ins = _loop_instructions(out.read_text())
+    asm, _ = compile_tu(TU, tmp_path, "dkdv_tu")
+    ins = _loop_instructions(asm)
     count = lambda name: sum(1 for i in ins if i == name)
     print("loop instructions:", len(ins),
           {n: count(n) for n in ("v_mfma_f32_32x32x16_bf16",

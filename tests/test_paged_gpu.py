@@ -1,4 +1,5 @@
-"""paged.hip on the GPU: K.attn_decode_paged and K.kv_page_write against
+"""The paged KV cache on the GPU (paged.hip, and decode.hip's paged
+instantiation): K.attn_decode_paged and K.kv_page_write against
 CPU references, and the model / engine wiring on a paged cache.
 
 The pool is larger than what the sequences own. Every unowned page and
@@ -100,6 +101,42 @@ def test_attn_decode_paged_matches_reference(dev, B, H, Hkv, lengths,
         worst = max(worst, err)
     print("paged decode %s worst row rel err %.3e" % (lengths, worst))
     assert worst < TOL
+
+
+# lengths of 512 at max_len 512: both launchers choose 2 splits, and the
+# dense split of 256 rows is the paged split of 4 pages — same tile order.
+# At 130 the dense kernel makes two 65-row splits, the paged one a 128-row
+# and a 2-row split.
+@pytest.mark.parametrize("lengths", [[512, 512], [512, 130]])
+def test_attn_decode_paged_matches_dense_kernel(dev, lengths):
+    """The dense decode kernel on the same rows, contiguous, with the same
+    capacity and max_len: the two instantiations of one body. Gated at the
+    kernel tolerance; bit equality is printed, not asserted."""
+    from metaflow_amd.ops import kernels as K
+
+    B, H, Hkv, max_len = 2, 4, 2, 512
+    q, kp, vp, table, rows = _paged_case(B, H, Hkv, lengths, max_len,
+                                         seed=13)
+    Lmax = table.size(1) * PAGE
+    kc = torch.full((B, Hkv, Lmax, 128), float("nan"), dtype=torch.bfloat16)
+    vc = torch.full_like(kc, float("nan"))
+    for b, (k, v) in enumerate(rows):
+        kc[b, :, :k.size(1)] = k
+        vc[b, :, :v.size(1)] = v
+    gq = q.to(dev)
+    o_p = K.attn_decode_paged(gq, kp.to(dev), vp.to(dev), table.to(dev),
+                              lengths, SCALE, max_len)
+    o_d = K.attn_decode_varlen(gq, kc.to(dev), vc.to(dev), lengths, SCALE,
+                               max_len=max_len)
+    torch.cuda.synchronize()
+    print("paged vs dense decode %s bit-equal: %s"
+          % (lengths, torch.equal(o_p, o_d)))
+    o_p, o_d = o_p.float().cpu(), o_d.float().cpu()
+    assert not torch.isnan(o_p).any() and not torch.isnan(o_d).any()
+    err = ((o_p - o_d).norm(dim=-1) / o_d.norm(dim=-1)).max().item()
+    print("paged vs dense decode %s worst per-row rel diff %.3e"
+          % (lengths, err))
+    assert err < TOL
 
 
 @pytest.mark.parametrize("S,pos", [(1, [0, 63, -1]), (70, [0, 60, 130])])
