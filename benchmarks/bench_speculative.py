@@ -37,9 +37,13 @@ def main():
     device = "cuda"
     torch.manual_seed(0)
     cfgs = {"llama3-8b": LlamaConfig.llama3_8b, "tiny": LlamaConfig.tiny}
+    target_cfg, draft_cfg = cfgs[args.target](), cfgs[args.draft]()
+    # the draft is fed the target's tokens: its embedding table must
+    # cover the target's vocabulary, or the lookup reads out of bounds
+    draft_cfg.vocab_size = target_cfg.vocab_size
     with torch.device(device):
-        target = LlamaForCausalLM(cfgs[args.target]()).eval()
-        draft = LlamaForCausalLM(cfgs[args.draft]()).eval()
+        target = LlamaForCausalLM(target_cfg).eval()
+        draft = LlamaForCausalLM(draft_cfg).eval()
     prompt = torch.randint(2, 1000, (1, args.prompt), device=device)
 
     torch.cuda.synchronize()

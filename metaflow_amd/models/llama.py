@@ -13,6 +13,8 @@ import torch
 import torch.nn as nn
 
 from ..ops import kernels as K
+from .generate import generate
+from .kv_cache import KVCache, PagedKVCache, PagedSlotView  # noqa: F401
 
 
 @dataclass
@@ -125,27 +127,8 @@ class DecoderLayer(nn.Module):
         qkv = self.qkv_proj(y)
         # one fused kernel: QKV split + bhsd transpose + RoPE
         q, k, v = K.rope_qkv(qkv, cos_t, sin_t, nq, nkv)
-        if isinstance(cache, PagedSlotView):
-            o = paged_cached_attention(q, k, v, cache, layer_idx,
-                                       1.0 / math.sqrt(hd))
-        elif cache is not None:
-            kc, vc, pos = cache.k[layer_idx], cache.v[layer_idx], \
-                cache.pos
-            kc[:, :, pos:pos + S] = k
-            vc[:, :, pos:pos + S] = v
-            if pos == 0:
-                o = K.attention(q, k, v)      # prefill: flash (padded
-                # to the 256 tile internally for unaligned prompts)
-            elif S == 1:
-                # one-token decode: split-K flash-decode straight over
-                # the cache allocation (decode.hip)
-                o = K.attn_decode(q, kc, vc, pos + 1,
-                                  1.0 / math.sqrt(hd))
-            else:
-                # S new rows at pos > 0 (speculative verify block, later
-                # prefill chunks): append kernel over the whole cache
-                # allocation (append.hip)
-                o = K.attn_append(q, kc, vc, pos, 1.0 / math.sqrt(hd))
+        if cache is not None:
+            o = cache.attend(layer_idx, q, k, v, S, 1.0 / math.sqrt(hd))
         elif cp_group is not None:
             from ..parallel.ring_attention import ring_attention
 
@@ -177,17 +160,8 @@ class DecoderLayer(nn.Module):
         v = v.view(B, 1, nkv, hd).transpose(1, 2)
         q = _rope_rows(q, c_rows, s_rows)
         k = _rope_rows(k, c_rows, s_rows)
-        if isinstance(cache, PagedKVCache):
-            o = paged_decode_attention(q, k, v, cache, layer_idx, pos_t,
-                                       lengths, 1.0 / math.sqrt(hd),
-                                       max_len)
-        else:
-            kc, vc = cache.k[layer_idx], cache.v[layer_idx]
-            bidx = torch.arange(B, device=res.device)
-            kc[bidx, :, pos_t] = k[:, :, 0]
-            vc[bidx, :, pos_t] = v[:, :, 0]
-            o = K.attn_decode_varlen(q.contiguous(), kc, vc, lengths,
-                                     1.0 / math.sqrt(hd), max_len=max_len)
+        o = cache.decode_attend(layer_idx, q, k, v, pos_t, lengths,
+                                1.0 / math.sqrt(hd), max_len)
         o = o.transpose(1, 2).reshape(B, 1, nq * hd)
         res, y = K.add_rmsnorm(res, self.o_proj(o), self.post_norm.weight,
                                self.post_norm.eps)
@@ -208,176 +182,11 @@ def _rope_rows(x, c, s):
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(x.dtype)
 
 
-class KVCache(object):
-    """Preallocated per-layer KV cache for autoregressive decode.
-
-    k/v: one [B, Hkv, max_len, 128] bf16 tensor per layer, filled
-    in-place as positions arrive; ``pos`` is the number of cached
-    positions (advanced once per model forward, not per layer).
-    """
-
-    def __init__(self, cfg, batch, max_len, device, dtype=torch.bfloat16):
-        self.k = [torch.zeros(batch, cfg.num_kv_heads, max_len,
-                              cfg.head_dim, device=device, dtype=dtype)
-                  for _ in range(cfg.num_layers)]
-        self.v = [torch.zeros_like(k) for k in self.k]
-        self.pos = 0
-        self.max_len = max_len
-
-
-class PagedKVCache(object):
-    """Paged KV cache for the serving engine: instead of max_len rows per
-    slot, sequences own 64-row pages of a shared pool and a block table
-    maps (slot, page index) -> pool page (ops/csrc/paged.hip).
-
-    k_pages/v_pages: one [num_pages, Hkv, 64, 128] tensor per layer (all
-    layers share one table: a page index means the same page in each).
-    ``table_host`` is the int32 [max_batch, ceil(max_len/64)] host mirror
-    the allocator edits; ``block_table`` is the persistent device copy the
-    kernels read, refreshed by ``sync()``. -1 = no page.
-
-    The free list is LIFO. Reservations only count pages (admission
-    control); pages are handed out by ``ensure``. Freed pages are not
-    cleared: rows past a sequence's length are never read.
-    """
-
-    PAGE = K.PAGE_ROWS
-
-    def __init__(self, cfg, num_pages, max_batch, max_len, device,
-                 dtype=torch.bfloat16):
-        self.k_pages = [torch.zeros(num_pages, cfg.num_kv_heads, self.PAGE,
-                                    cfg.head_dim, device=device,
-                                    dtype=dtype)
-                        for _ in range(cfg.num_layers)]
-        self.v_pages = [torch.zeros_like(k) for k in self.k_pages]
-        self.num_pages = num_pages
-        self.max_batch = max_batch
-        self.max_len = max_len
-        self.pages_per_seq = -(-max_len // self.PAGE)
-        self.table_host = torch.full((max_batch, self.pages_per_seq), -1,
-                                     dtype=torch.int32)
-        # its own storage even on the CPU: the mirror is edited freely,
-        # the kernels' table changes only in sync()
-        self.block_table = torch.full_like(self.table_host, -1,
-                                           device=device)
-        self._free = list(range(num_pages - 1, -1, -1))  # pop() -> page 0
-        self._owned = [[] for _ in range(max_batch)]
-        self._reserved = 0
-        self._dirty = False
-
-    @property
-    def free_pages(self):
-        return len(self._free)
-
-    def reserve(self, n_pages):
-        """Count n_pages against the pool; False if they do not fit."""
-        if self._reserved + n_pages > self.num_pages:
-            return False
-        self._reserved += n_pages
-        return True
-
-    def release_reservation(self, n_pages):
-        assert 0 <= n_pages <= self._reserved, "released more than reserved"
-        self._reserved -= n_pages
-
-    def ensure(self, slot, n_rows):
-        """Allocate pages until ``slot`` covers rows 0 .. n_rows-1."""
-        need = -(-n_rows // self.PAGE)
-        assert need <= self.pages_per_seq, "rows beyond the slot capacity"
-        owned = self._owned[slot]
-        while len(owned) < need:
-            assert self.num_pages - len(self._free) < self._reserved, \
-                "page allocation beyond the reservation"
-            page = self._free.pop()
-            self.table_host[slot, len(owned)] = page
-            owned.append(page)
-            self._dirty = True
-
-    def free_slot(self, slot):
-        """Return the slot's pages to the pool, reset its entries."""
-        owned = self._owned[slot]
-        assert owned, "double free: slot %d owns no pages" % slot
-        self._free.extend(reversed(owned))
-        self.table_host[slot, :len(owned)] = -1
-        self._owned[slot] = []
-        self._dirty = True
-
-    def sync(self):
-        """One copy of the host table into the device table, only when
-        the host table changed since the last sync."""
-        if self._dirty:
-            self.block_table.copy_(self.table_host)
-            self._dirty = False
-
-
-class PagedSlotView(object):
-    """Single-slot view of a PagedKVCache for the models' forward (the
-    role serving._SlotView plays for KVCache): prefill chunks of one
-    request write through it and advance ``pos``."""
-
-    def __init__(self, paged, slot):
-        self.paged = paged
-        self.slot = slot
-        self.pos = 0
-
-
-def paged_cached_attention(q, k, v, view, layer_idx, scale):
-    """Attention of a batch-1 forward over a PagedSlotView: write the S
-    new K/V rows at view.pos, then attend. The first chunk (pos 0) is
-    the flash prefill on the fresh tensors; a one-token step is the paged
-    decode kernel; a later chunk is the paged append kernel, which reads
-    the slot's pages in place through the block table
-    (append.hip, paged instantiation)."""
-    pc, slot, pos = view.paged, view.slot, view.pos
-    S = q.size(2)
-    assert q.size(0) == 1, "a paged slot view holds one sequence"
-    kp, vp = pc.k_pages[layer_idx], pc.v_pages[layer_idx]
-    table_row = pc.block_table[slot:slot + 1]
-    K.kv_page_write(k, v, kp, vp, table_row, [pos])
-    if pos == 0:
-        return K.attention(q, k, v)
-    if S == 1:
-        return K.attn_decode_paged(q.contiguous(), kp, vp, table_row,
-                                   [pos + 1], scale, pc.max_len)
-    return K.attn_append_paged(q.contiguous(), kp, vp, table_row, [pos],
-                               scale)
-
-
-def decode_positions(cache, positions, device):
-    """Device tensors of one batched decode step: (pos_t, lengths,
-    rope_rows). On a KVCache every slot writes at positions[b] (inactive
-    slots pass 0). On a PagedKVCache a position of -1 marks a slot that
-    does not take part: pos_t (int32, the write offsets) keeps the -1 so
-    the write skips it, its length is 0 and its RoPE row is clamped to
-    0. No host read either way."""
-    pos_t = torch.as_tensor(positions, device=device, dtype=torch.long)
-    if isinstance(cache, PagedKVCache):
-        rope_rows = pos_t.clamp(min=0)
-        return (pos_t.to(torch.int32), (pos_t + 1).to(torch.int32),
-                rope_rows)
-    return pos_t, (pos_t + 1).to(torch.int32), pos_t
-
-
-def paged_decode_attention(q, k, v, cache, layer_idx, pos_t, lengths,
-                           scale, max_len=None):
-    """One layer of the batched decode step on a PagedKVCache: one
-    kv_page_write of every slot's new row, one paged flash-decode. The
-    split count always comes from a capacity (max_len or the cache's),
-    so eager and captured steps launch identical grids."""
-    kp, vp = cache.k_pages[layer_idx], cache.v_pages[layer_idx]
-    K.kv_page_write(k, v, kp, vp, cache.block_table, pos_t)
-    return K.attn_decode_paged(q.contiguous(), kp, vp, cache.block_table,
-                               lengths, scale,
-                               cache.max_len if max_len is None
-                               else max_len)
-
-
 def _attn_with_cache(q, k_all, v_all, scale, pos):
-    """Eager fp32 reference for the s new queries (global positions
-    pos..pos+s-1) against the T = pos+s cached rows in k_all/v_all.
-    Kept as an alias of K.attn_append_ref for callers and tests that
-    pass pre-sliced caches; no model path uses it — cached forwards go
-    through K.attn_append (HIP kernel on GPU, this formula on CPU)."""
+    """Alias of K.attn_append_ref with no caller left in the tree. It
+    stays for one revision because the previous revision of
+    tests/test_attn_append.py imports it at module level, and that
+    suite has to keep running against this tree; delete it next."""
     return K.attn_append_ref(q, k_all, v_all, pos, scale)
 
 
@@ -478,8 +287,8 @@ class LlamaForCausalLM(nn.Module):
         host reads and is hipGraph-capturable: the serving engine
         captures it once and replays per token (decode is launch-bound;
         see serving.ContinuousBatcher(graph=True))."""
-        pos_t, lengths, rope_rows = decode_positions(cache, positions,
-                                                     tokens.device)
+        pos_t, lengths, rope_rows = cache.decode_positions(positions,
+                                                           tokens.device)
         c_rows = self.cos_t[rope_rows]
         s_rows = self.sin_t[rope_rows]
         res = self.embed(tokens)
@@ -492,32 +301,9 @@ class LlamaForCausalLM(nn.Module):
                              self.final_norm.eps)
         return self.lm_head(x)
 
-    @torch.no_grad()
     def generate(self, tokens, max_new_tokens, temperature=0.0,
                  top_k=None):
-        """Autoregressive decode with a KV cache: flash-kernel prefill
-        (when the prompt length is 64-aligned), cached attention for the
-        one-token decode steps. temperature=0 is greedy."""
-        B, S0 = tokens.shape
-        cache = KVCache(self.cfg, B, S0 + max_new_tokens,
-                        tokens.device,
-                        dtype=self.embed.weight.dtype)
-        out = tokens
-        logits = self.forward(tokens, cache=cache)
-        for _ in range(max_new_tokens):
-            last = logits[:, -1].float()
-            if temperature and temperature > 0:
-                last = last / temperature
-                if top_k:
-                    kth = torch.topk(last, top_k, dim=-1).values[:, -1:]
-                    last = last.masked_fill(last < kth, float("-inf"))
-                probs = torch.softmax(last, dim=-1)
-                nxt = torch.multinomial(probs, 1)
-            else:
-                nxt = last.argmax(dim=-1, keepdim=True)
-            out = torch.cat([out, nxt], dim=1)
-            logits = self.forward(nxt, cache=cache)
-        return out
+        return generate(self, tokens, max_new_tokens, temperature, top_k)
 
     def num_params(self):
         return sum(p.numel() for p in self.parameters())

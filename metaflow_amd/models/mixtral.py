@@ -10,15 +10,15 @@ point-to-point and uses all 7 links concurrently — better suited to the
 topology than ring collectives.
 """
 
+import math
 from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 
 from ..ops import kernels as K
-from .llama import (Linear, PagedKVCache, PagedSlotView, RMSNorm,
-                    decode_positions, paged_cached_attention,
-                    paged_decode_attention)
+from .generate import generate
+from .llama import Linear, RMSNorm, _rope_rows
 
 
 @dataclass
@@ -269,30 +269,9 @@ class MixtralDecoderLayer(nn.Module):
                     cos_t, sin_t).transpose(1, 2)
         v = self.v_proj(y).view(B, S, cfg.num_kv_heads,
                                 cfg.head_dim).transpose(1, 2)
-        if isinstance(cache, PagedSlotView):
-            import math
-
-            o = paged_cached_attention(q, kk, v, cache, layer_idx,
-                                       1.0 / math.sqrt(cfg.head_dim))
-        elif cache is not None:
-            kc, vc, pos = cache.k[layer_idx], cache.v[layer_idx], cache.pos
-            kc[:, :, pos:pos + S] = kk
-            vc[:, :, pos:pos + S] = v
-            if pos == 0:
-                o = K.attention(q, kk, v)  # flash prefill (any S; the
-                # wrapper pads unaligned seqlens to the 256 tile)
-            elif S == 1:
-                import math
-
-                o = K.attn_decode(q.contiguous(), kc, vc, pos + 1,
-                                  1.0 / math.sqrt(cfg.head_dim))
-            else:
-                import math
-
-                # S new rows at pos > 0: append kernel over the whole
-                # cache allocation (append.hip)
-                o = K.attn_append(q.contiguous(), kc, vc, pos,
-                                  1.0 / math.sqrt(cfg.head_dim))
+        if cache is not None:
+            o = cache.attend(layer_idx, q, kk, v, S,
+                             1.0 / math.sqrt(cfg.head_dim))
         else:
             o = K.attention(q, kk, v)
         o = o.transpose(1, 2).reshape(B, S, cfg.num_heads * cfg.head_dim)
@@ -306,10 +285,6 @@ class MixtralDecoderLayer(nn.Module):
         """Continuous-batching decode for the MoE layer: per-slot cache
         scatter + varlen flash-decode; experts route per decoded
         token."""
-        import math
-
-        from .llama import _rope_rows
-
         cfg = self.cfg
         B = x.size(0)
         hd = cfg.head_dim
@@ -320,17 +295,8 @@ class MixtralDecoderLayer(nn.Module):
         v = self.v_proj(y).view(B, 1, cfg.num_kv_heads, hd).transpose(1, 2)
         q = _rope_rows(q, c_rows, s_rows)
         k = _rope_rows(k, c_rows, s_rows)
-        if isinstance(cache, PagedKVCache):
-            o = paged_decode_attention(q, k, v, cache, layer_idx, pos_t,
-                                       lengths, 1.0 / math.sqrt(hd),
-                                       max_len)
-        else:
-            kc, vc = cache.k[layer_idx], cache.v[layer_idx]
-            bidx = torch.arange(B, device=x.device)
-            kc[bidx, :, pos_t] = k[:, :, 0]
-            vc[bidx, :, pos_t] = v[:, :, 0]
-            o = K.attn_decode_varlen(q.contiguous(), kc, vc, lengths,
-                                     1.0 / math.sqrt(hd), max_len=max_len)
+        o = cache.decode_attend(layer_idx, q, k, v, pos_t, lengths,
+                                1.0 / math.sqrt(hd), max_len)
         o = o.transpose(1, 2).reshape(B, 1, cfg.num_heads * hd)
         x = res + self.o_proj(o)
         x = x + self.moe(self.post_norm(x))
@@ -386,8 +352,8 @@ class MixtralForCausalLM(nn.Module):
         MoE router's token dispatch is shape-dynamic — so the serving
         engine keeps Mixtral on the eager decode path
         (graph_safe_decode stays False)."""
-        pos_t, lengths, rope_rows = decode_positions(cache, positions,
-                                                     tokens.device)
+        pos_t, lengths, rope_rows = cache.decode_positions(positions,
+                                                           tokens.device)
         c_rows = self.cos_t[rope_rows]
         s_rows = self.sin_t[rope_rows]
         x = self.embed(tokens)
@@ -396,31 +362,9 @@ class MixtralForCausalLM(nn.Module):
                                   lengths, max_len=max_len)
         return self.lm_head(self.final_norm(x))
 
-    @torch.no_grad()
     def generate(self, tokens, max_new_tokens, temperature=0.0,
                  top_k=None):
-        """Autoregressive MoE decode with a KV cache (same contract as
-        LlamaForCausalLM.generate; experts route per decoded token)."""
-        from .llama import KVCache
-
-        B, S0 = tokens.shape
-        cache = KVCache(self.cfg, B, S0 + max_new_tokens, tokens.device,
-                        dtype=self.embed.weight.dtype)
-        out = tokens
-        logits = self.forward(tokens, cache=cache)
-        for _ in range(max_new_tokens):
-            last = logits[:, -1].float()
-            if temperature and temperature > 0:
-                last = last / temperature
-                if top_k:
-                    kth = torch.topk(last, top_k, dim=-1).values[:, -1:]
-                    last = last.masked_fill(last < kth, float("-inf"))
-                nxt = torch.multinomial(torch.softmax(last, -1), 1)
-            else:
-                nxt = last.argmax(dim=-1, keepdim=True)
-            out = torch.cat([out, nxt], dim=1)
-            logits = self.forward(nxt, cache=cache)
-        return out
+        return generate(self, tokens, max_new_tokens, temperature, top_k)
 
     def num_params(self):
         return sum(p.numel() for p in self.parameters())

@@ -17,7 +17,11 @@ our own kernels — no reference counterpart, SURVEY §2.4 note):
   static batch;
 * opt-in paging (``num_pages``): the slots share a pool of 64-row pages
   through a device block table instead of reserving max_len rows each
-  (models/llama.py PagedKVCache, paged.hip).
+  (models/kv_cache.py PagedKVCache, paged.hip).
+
+The engine never asks which cache it holds: admission, page allocation,
+release and the position of a slot that is not decoding are hooks of
+the cache (models/kv_cache.py).
 
 Greedy decoding is token-exact with ``model.generate`` per request.
 """
@@ -35,16 +39,6 @@ class Request(object):
         self.max_new = int(max_new_tokens)
         self.generated = []
         self.done = False
-
-
-class _SlotView(object):
-    """Single-slot view of the batched KV cache: the model's prefill
-    path writes through it in place (views, no copies)."""
-
-    def __init__(self, cache, slot):
-        self.k = [t[slot:slot + 1] for t in cache.k]
-        self.v = [t[slot:slot + 1] for t in cache.v]
-        self.pos = 0
 
 
 class ContinuousBatcher(object):
@@ -68,7 +62,7 @@ class ContinuousBatcher(object):
 
         num_pages: None keeps the dense cache (max_len rows reserved per
         slot). An integer selects the paged cache instead: a pool of
-        that many 64-row pages shared by all slots (models/llama.py
+        that many 64-row pages shared by all slots (models/kv_cache.py
         PagedKVCache, ops/csrc/paged.hip), so the number of concurrent
         requests is bounded by the rows they can actually reach, not by
         max_batch * max_len. Admission is FIFO and reserves
@@ -78,7 +72,7 @@ class ContinuousBatcher(object):
         Physical pages are allocated lazily as rows are written."""
         import torch
 
-        from .models.llama import KVCache, PagedKVCache
+        from .models.kv_cache import KVCache, PagedKVCache
 
         self.model = model
         self.max_batch = max_batch
@@ -90,7 +84,6 @@ class ContinuousBatcher(object):
             self.cache = PagedKVCache(model.cfg, num_pages, max_batch,
                                       max_len, device,
                                       dtype=model.embed.weight.dtype)
-            self._reserved = [0] * max_batch  # pages reserved per slot
         else:
             self.cache = KVCache(model.cfg, max_batch, max_len, device,
                                  dtype=model.embed.weight.dtype)
@@ -98,7 +91,7 @@ class ContinuousBatcher(object):
         self.slots = [None] * max_batch     # Request or None
         self.next_token = [0] * max_batch   # token to feed next step
         self.prefill_chunk = prefill_chunk
-        self._views = [None] * max_batch    # _SlotView while prefilling
+        self._views = [None] * max_batch    # slot view while prefilling
         self._prefill_done = [0] * max_batch  # prompt tokens cached
         self.queue = deque()
         self._torch = torch
@@ -121,10 +114,10 @@ class ContinuousBatcher(object):
         torch = self._torch
         self._tok_buf = torch.zeros(self.max_batch, 1, dtype=torch.long,
                                     device=self.device)
-        self._pos_buf = torch.zeros(self.max_batch, dtype=torch.long,
-                                    device=self.device)
-        if self.paged:
-            self._pos_buf.fill_(-1)  # no slot takes part while capturing
+        # no slot decodes while capturing
+        self._pos_buf = torch.full((self.max_batch,),
+                                   self.cache.idle_position(0),
+                                   dtype=torch.long, device=self.device)
         # warmup on a side stream (allocator primes its graph pool)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -149,11 +142,8 @@ class ContinuousBatcher(object):
                                                 device=self.device))
             self._graph.replay()
             return self._logits_buf
-        if self.paged:
-            # capacity-sized splits, as in the captured step: eager and
-            # replayed decodes launch identical grids
-            return self.model.decode_step(tokens, self.cache, positions,
-                                          max_len=self.max_len)
+        # no max_len: the dense cache sizes its splits from the lengths,
+        # the paged cache from its capacity, as in the captured step
         return self.model.decode_step(tokens, self.cache, positions)
 
     def submit(self, prompt_tokens, max_new_tokens):
@@ -162,55 +152,28 @@ class ContinuousBatcher(object):
         return req
 
     # ------------------------------------------------------------- internals
-    def _view(self, slot):
-        if self.paged:
-            from .models.llama import PagedSlotView
-
-            return PagedSlotView(self.cache, slot)
-        return _SlotView(self.cache, slot)
-
-    def _reserve_head(self, slot):
-        """Paged admission of the queue's head into ``slot``: reserve
-        every page the request can ever touch, or leave it waiting."""
-        req = self.queue[0]
-        total = len(req.prompt) + req.max_new
-        assert total <= self.max_len, \
-            "request longer than the slot capacity"
-        need = -(-total // self.cache.PAGE)
-        assert need <= self.cache.num_pages, \
-            "request larger than the page pool"
-        if not self.cache.reserve(need):
-            return False
-        self._reserved[slot] = need
-        return True
-
-    def _ensure_rows(self, slot, n_rows):
-        """Paged cache: give ``slot`` the pages for rows 0 .. n_rows-1
-        before a prefill writes them (no-op on the dense cache)."""
-        if self.paged:
-            self.cache.ensure(slot, n_rows)
-            self.cache.sync()
-
     def _admit(self):
         torch = self._torch
         for slot in range(self.max_batch):
             if self.slots[slot] is not None or not self.queue:
                 continue
-            if self.paged and not self._reserve_head(slot):
+            req = self.queue[0]
+            if not self.cache.admit(slot, len(req.prompt) + req.max_new):
                 return  # FIFO: nobody overtakes the waiting head
-            req = self.queue.popleft()
+            self.queue.popleft()
             assert len(req.prompt) + req.max_new <= self.max_len, \
                 "request longer than the slot capacity"
             self.slots[slot] = req
             if self.prefill_chunk is not None:
                 # chunked: cache nothing yet; step() feeds chunks
-                self._views[slot] = self._view(slot)
+                self._views[slot] = self.cache.slot_view(slot)
                 self._prefill_done[slot] = 0
                 self.positions[slot] = 0
                 continue
             prompt = torch.tensor([req.prompt], device=self.device)
-            view = self._view(slot)
-            self._ensure_rows(slot, len(req.prompt))
+            view = self.cache.slot_view(slot)
+            self.cache.ensure(slot, len(req.prompt))
+            self.cache.sync()
             with torch.no_grad():
                 logits = self.model(prompt, cache=view)
             nxt = int(logits[0, -1].float().argmax())
@@ -233,7 +196,8 @@ class ContinuousBatcher(object):
             a = self._prefill_done[slot]
             b = min(a + self.prefill_chunk, len(req.prompt))
             chunk = torch.tensor([req.prompt[a:b]], device=self.device)
-            self._ensure_rows(slot, b)
+            self.cache.ensure(slot, b)
+            self.cache.sync()
             with torch.no_grad():
                 logits = self.model(chunk, cache=view)
             self._prefill_done[slot] = b
@@ -248,10 +212,7 @@ class ContinuousBatcher(object):
                 self._finish(slot)
 
     def _finish(self, slot):
-        if self.paged:
-            self.cache.free_slot(slot)
-            self.cache.release_reservation(self._reserved[slot])
-            self._reserved[slot] = 0
+        self.cache.release(slot)
         self.slots[slot].done = True
         self.slots[slot] = None
         self.positions[slot] = 0
@@ -268,25 +229,18 @@ class ContinuousBatcher(object):
             self._prefill_step()
         active = [i for i, r in enumerate(self.slots) if r is not None
                   and self._views[i] is None]
-        # the batched decode scatters a (garbage) K/V row for EVERY
-        # slot at its position; a mid-prefill slot must aim that write
-        # at its next-unwritten row — the following prefill chunk
-        # overwrites it, so the cached prefix stays intact
-        pos_list = list(self.positions)
-        for i in range(self.max_batch):
-            if self._views[i] is not None:
-                pos_list[i] = self._prefill_done[i]
         if not active:
             return 0
-        if self.paged:
-            # no garbage-row trick here: slots that take no part pass
-            # -1 (nothing written, length 0); a slot about to write the
-            # first row of a page gets that page now
-            pos_list = [-1] * self.max_batch
-            for i in active:
-                pos_list[i] = self.positions[i]
-                self.cache.ensure(i, self.positions[i] + 1)
-            self.cache.sync()
+        # every slot starts at the cache's idle position for the rows it
+        # has cached: _prefill_done for a mid-prefill slot, and 0 for a
+        # free one (_finish resets _prefill_done along with positions).
+        # A decoding slot gets the page of the row it is about to write
+        pos_list = [self.cache.idle_position(n)
+                    for n in self._prefill_done]
+        for i in active:
+            self.cache.ensure(i, self.positions[i] + 1)
+            pos_list[i] = self.positions[i]
+        self.cache.sync()
         tokens = torch.zeros(self.max_batch, 1, dtype=torch.long,
                              device=self.device)
         for i in active:

@@ -16,7 +16,7 @@ kernel rounds P to bf16 for the MFMA where the decode kernel keeps it
 fp32, so a near-tied argmax may resolve differently between the two.
 
 Cache bookkeeping leans on KVCache.pos being the single read boundary
-(models/llama.py): rejected proposal rows stay in the cache allocation
+(models/kv_cache.py): rejected proposal rows stay in the cache allocation
 but are never read once ``pos`` is rolled back, so rollback is free.
 """
 
@@ -39,8 +39,6 @@ def speculative_generate(target, draft, tokens, max_new_tokens,
     # root, and a module-level torch import would load torch into every
     # small task subprocess (the bisected 10x startup regression)
     import torch
-
-    from .models.llama import KVCache
 
     assert tokens.dim() == 2 and tokens.size(0) == 1, \
         "speculative_generate is per-sequence (B=1)"

@@ -3,7 +3,6 @@ offsets, and independence from cache rows past the visible range."""
 
 import torch
 
-from metaflow_amd.models.llama import _attn_with_cache
 from metaflow_amd.ops import kernels as K
 
 SCALE = 0.0883
@@ -21,8 +20,8 @@ def test_int_pos_is_bit_identical_to_attn_with_cache():
     q, kc, vc = _inputs()
     pos, S = 9, q.size(2)
     o = K.attn_append(q, kc, vc, pos, SCALE)
-    ref = _attn_with_cache(q, kc[:, :, :pos + S], vc[:, :, :pos + S], SCALE,
-                           pos)
+    ref = K.attn_append_ref(q, kc[:, :, :pos + S], vc[:, :, :pos + S], pos,
+                            SCALE)
     assert o.dtype == torch.bfloat16 and o.shape == q.shape
     assert torch.equal(o, ref)
 
@@ -33,8 +32,8 @@ def test_pos_list_equals_per_sequence_loop():
     pos = [0, 7]
     o = K.attn_append(q, kc, vc, pos, SCALE)
     for b, p in enumerate(pos):
-        ref = _attn_with_cache(q[b:b + 1], kc[b:b + 1, :, :p + S],
-                               vc[b:b + 1, :, :p + S], SCALE, p)
+        ref = K.attn_append_ref(q[b:b + 1], kc[b:b + 1, :, :p + S],
+                                vc[b:b + 1, :, :p + S], p, SCALE)
         assert torch.equal(o[b:b + 1], ref)
     # a tensor of offsets is the same call
     assert torch.equal(
