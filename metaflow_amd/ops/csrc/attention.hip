@@ -20,16 +20,20 @@
 //    come out transposed (d in the registers, the row on the lane); each
 //    epilogue turns them back through LDS tiles that are free by then
 //    (store_acc_tile_t, store_acc_tile_t_bf16);
-//  * LDS holds only the streamed operand tiles, in the 16-wide PANEL
-//    layout below, which serves contiguous row-fragment reads and
-//    hardware-transposed fragment reads from the same copy;
+//  * LDS holds only the streamed operand tiles, in the dual-use IMAGE A
+//    of attn_lds_image.h (8-row x 32-column subtiles, XOR-swizzled),
+//    which serves the row-fragment reads (ds_read_b128) and the
+//    hardware-transposed fragment reads (ds_read_b64_tr_b16) from one
+//    copy, both free of bank conflicts. The 16-wide PANEL layout below
+//    remains for the append kernels, the dK/dV V image and the probe;
 //  * one block per (256-row tile, head, batch element) on a 1-D grid,
 //    dispatched heavy causal tiles first (block_coord).
 // col_to_afrags and store_acc_tile (the untransposed forms) remain for
 // the append kernels (col_to_afrags) and the layout probe (both).
 //
 // MFMA 32x32x16 layouts (probed on HW by dbg_mfma32_kernel; the panel /
-// transposed-read / col_to_afrags chain by dbg_attn_layout_kernel):
+// transposed-read / col_to_afrags chain by dbg_attn_layout_kernel, the
+// image / acc_to_bfrags chain by dbg_attn_image_kernel):
 //  A (32x16): lane holds A[lane&31][(lane>>5)*8 + i]
 //  B (16x32): lane holds B[(lane>>5)*8 + i][lane&31]
 //  C (32x32): col = lane&31, row = c_row(reg, lane>>5)
@@ -39,6 +43,7 @@
 // end-padded keys are causally masked for every real query row).
 
 #include "common.h"
+#include "attn_lds_image.h"
 
 #define ATT_D 128
 
@@ -189,6 +194,68 @@ DEV void tr_load_bfrags(BFrag bfr[4], const short* tile, int row0,
   }
 }
 
+// ================= dual-use image A (attn_lds_image.h) ====================
+// The streamed tiles of the three train kernels. Addresses are BYTES and
+// come from the header's functions: a lane keeps two row-read bases (k-step
+// parity) and two transposed-read bases (first / second read of a
+// fragment); tile row group, k-step and d block are instruction
+// immediates.
+
+// 32-bit LDS address of a __shared__ object (low half of the generic
+// pointer), the form ds_* instructions take
+DEV unsigned int lds_addr(const void* p) {
+  return (unsigned int)(unsigned long long)p;
+}
+
+// transposed read at a lane base plus a compile-time byte offset (imm
+// must fold to a constant: call it from fully unrolled code only). Same
+// waiting rules as tr_read.
+DEV unsigned long long tr_read_imm(unsigned int base, int imm) {
+  unsigned long long out;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(out)
+               : "v"(base), "i"(imm));
+  return out;
+}
+
+// row fragment: row 32t + l32, d = 16s + 8hi .. +7; rb0 / rb1 are the
+// lane's lds_img::row_base_a(lane, 0 / 1)
+DEV bf16x8 img_row_frag(const short* tile, int rb0, int rb1, int t, int s) {
+  return *(const bf16x8*)((const char*)tile + ((s & 1) ? rb1 : rb0)
+                          + lds_img::row_imm_a(t, s));
+}
+
+// the 8 transposed reads of k-step ks (tile rows 16ks .. 16ks+15): this
+// lane's four fragments, n = 0..3: d columns 32n + l32, rows 16ks + 8hi +
+// (0..7). tb0 / tb1 = lds_addr(tile) + lds_img::tr_base_a(lane, 0 / 1).
+// Waiting is the caller's job, as with tr_load_bfrags.
+DEV void img_tr_load(BFrag bfr[4], unsigned int tb0, unsigned int tb1,
+                     int ks) {
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    bfr[n].u[0] = tr_read_imm(tb0, lds_img::tr_imm_a(ks, n));
+    bfr[n].u[1] = tr_read_imm(tb1, lds_img::tr_imm_a(ks, n));
+  }
+}
+
+// stage a [ROWS][128] row-major global tile into image A, lanes walking
+// rows (stage_panel's thread map)
+template <int ROWS, int BLOCK>
+DEV void stage_image(short* dst, const short* src,
+                     long long src_row_stride) {
+  constexpr int TOT = ROWS * 16;  // 16-byte chunks
+#pragma unroll
+  for (int it = 0; it < (TOT + BLOCK - 1) / BLOCK; ++it) {
+    const int idx = it * BLOCK + threadIdx.x;
+    if (idx < TOT) {
+      const int r = lds_img::stage_walk_row(ROWS, idx);
+      const int ch = lds_img::stage_walk_ch(ROWS, idx);
+      bf16x8 v = *(const bf16x8*)(src + r * src_row_stride + ch * 8);
+      *(bf16x8*)((char*)dst + lds_img::off_a(r, ch)) = v;
+    }
+  }
+}
+
 // ---- accumulator-tile epilogue ----
 DEV void put_elem(short* p, float x) { *p = f2bf(x); }
 DEV void put_elem(float* p, float x) { *p = x; }
@@ -200,9 +267,9 @@ DEV void put_elem(float* p, float x) { *p = x; }
 // keeps per-row scalars in the lane that owns the row). Used by the
 // layout probe; the train kernels accumulate the
 // transposed product and store through store_acc_tile_t /
-// store_acc_tile_t_bf16 below. tr_load_bfrags above serves dq and the
-// probe; the forward and dkdv keep open-coded copies of the same
-// addressing.
+// store_acc_tile_t_bf16 below. tr_load_bfrags above serves the append
+// kernels and the probe; the train kernels read image A (img_tr_load; dkdv
+// keeps an open-coded copy of that addressing).
 template <bool ROW_SCALE, typename T>
 DEV void store_acc_tile(T* dst, long long off0, int row0, const f16f acc[4],
                         int l32, int hi, float lane_scale = 1.f) {
@@ -357,7 +424,7 @@ DEV BlockCoord block_coord(int T, int H) {
 // One block per (q tile, h, b) in heavy-first order (block_coord), 8 waves
 // x 32 q rows; each lane keeps its own q row in registers (8 x bf16x8)
 // and streams 64-row K/V tiles through LDS.
-// LDS: K and V panel tiles, double-buffered = 2 x 2 x 16 KiB = 64 KiB.
+// LDS: K and V tiles in image A, double-buffered = 2 x 2 x 16 KiB = 64 KiB.
 //
 // Q ROW ON THE LANE, BOTH PRODUCTS. S^T = K·Q^T leaves the lane's q row
 // of scores in its registers (kv on the rows), which is already the
@@ -378,10 +445,10 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
     float* __restrict__ lse, int B, int H, int Hkv, int S, float scale,
     int causal) {
   constexpr int BQ = 256, BKV = 64;  // 8 waves x 32 q rows
-  // double-buffered K/V tiles in the 16-wide PANEL layout [8][64][16]:
-  // staging is pure vec8 writes, K A-fragments are contiguous panel
-  // reads, V B-fragments come from ds_read_b64_tr_b16 (no transposed
-  // copy). Stage j+1 overlaps compute on j (async-stage split).
+  // double-buffered K/V tiles in image A (attn_lds_image.h): staging is
+  // pure vec8 writes, K A-fragments are conflict-free 16-byte row reads,
+  // V^T A-fragments come from ds_read_b64_tr_b16 of the same copy. Stage
+  // j+1 overlaps compute on j (async-stage split).
   __shared__ short kp[2][BKV * ATT_D];
   __shared__ short vp[2][BKV * ATT_D];
 
@@ -420,9 +487,16 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int idx = u * BLOCK + tid;
-    stg_r[u] = idx / 16;
-    stg_c8[u] = idx % 16;
+    stg_r[u] = lds_img::stage16_row(idx);
+    stg_c8[u] = lds_img::stage16_ch(idx);
   }
+  // image addresses (bytes): the thread's staging chunk (slot u is 32 rows
+  // = 8192 bytes further), the lane's row-read and transposed-read bases
+  const int stg_off = lds_img::stage16_addr_a(tid);
+  const int rb0 = lds_img::row_base_a(lane, 0);
+  const int rb1 = lds_img::row_base_a(lane, 1);
+  const unsigned int tb0 = lds_addr(&vp[0][0]) + lds_img::tr_base_a(lane, 0);
+  const unsigned int tb1 = lds_addr(&vp[0][0]) + lds_img::tr_base_a(lane, 1);
 
   // global loads and LDS writes of a tile are split so the loads for
   // tile j+1 are in flight during the MFMAs on tile j; kept as macros
@@ -440,10 +514,9 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
 #define MFX_STAGE_WRITE(buf)                                             \
   {                                                                      \
     _Pragma("unroll") for (int u = 0; u < 2; ++u) {                      \
-      const int pel_ = (stg_c8[u] >> 1) * (BKV * 16) + stg_r[u] * 16     \
-                       + (stg_c8[u] & 1) * 8;                            \
-      *(bf16x8*)(kp[buf] + pel_) = stg_k[u];                             \
-      *(bf16x8*)(vp[buf] + pel_) = stg_v[u];                             \
+      const int pel_ = stg_off + u * 8192;                               \
+      *(bf16x8*)((char*)kp[buf] + pel_) = stg_k[u];                      \
+      *(bf16x8*)((char*)vp[buf] + pel_) = stg_v[u];                      \
     }                                                                    \
   }
 
@@ -468,29 +541,36 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
       st[t] = (f16f){};
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        bf16x8 kf = frag8_panel<BKV>(kp[cur], t * 32 + l32,
-                                     s * 16 + hi * 8);
+        bf16x8 kf = img_row_frag(kp[cur], rb0, rb1, t, s);
         st[t] = mfma32(kf, q_reg[s], st[t]);
       }
     }
 
     // ---- scale + causal mask + in-register online softmax ----
     // lane's value (t, r) is S[my_qrow][kv = j*64 + t*32 + c_row(r,hi)]
+    // The mask is a pass of its own behind a block-uniform (scalar)
+    // branch: only the block's 4 diagonal tiles can lose an element; all
+    // others run no compare and no select. (Narrowing the predicate to
+    // the wave's own diagonal measured no faster: docs/KERNELS.md.)
     const bool diag = causal && (j * BKV + BKV > qb * BQ);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[t][r] *= scale;
+    if (diag) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kvg = j * BKV + t * 32 + c_row(r, hi);
+          if (kvg > my_qrow) st[t][r] = -INFINITY;
+        }
+    }
     float pmax = -INFINITY;
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float sv = st[t][r] * scale;
-        if (diag) {
-          const int kvg = j * BKV + t * 32 + c_row(r, hi);
-          if (kvg > my_qrow) sv = -INFINITY;
-        }
-        st[t][r] = sv;
-        pmax = fmaxf(pmax, sv);
-      }
-    }
+      for (int r = 0; r < 16; ++r) pmax = fmaxf(pmax, st[t][r]);
     pmax = half_pair_max(pmax);
     const float newm = fmaxf(m_run, pmax);
     const float rescale = __expf(m_run - newm);
@@ -520,23 +600,15 @@ __global__ __launch_bounds__(512) void attn_fwd_v2_kernel(
     acc_to_bfrags(st[1], pb + 2);
 
     // ---- PV: O^T(128d x 32q) += V^T(128d x 64kv) @ P^T(64kv x 32q) ----
-    // V^T A-fragments via hardware transpose: same addressing as
-    // tr_load_bfrags<BKV> (derivation there), open-coded because the
-    // helper form measured 0.6% slower here (3.24 vs 3.22 ms at
-    // B=8 H=32 S=4096) with an identical main loop
+    // V^T A-fragments via hardware transpose of the image (img_tr_load:
+    // two lane bases, k-step and d block as immediates)
     {
-      const int tr_lane_off = (((lane >> 2) & 3) * 16) + (lane & 3) * 4;
-      const int tr_panel = ((lane >> 4) & 1) * (BKV * 16);
+      const unsigned int tbc0 = tb0 + cur * (BKV * ATT_D * 2);
+      const unsigned int tbc1 = tb1 + cur * (BKV * ATT_D * 2);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         BFrag bfr[4];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          const int base = n * 2 * (BKV * 16) + tr_panel
-                           + (ks * 16 + hi * 8) * 16 + tr_lane_off;
-          bfr[n].u[0] = tr_read(vp[cur] + base);
-          bfr[n].u[1] = tr_read(vp[cur] + base + 4 * 16);
-        }
+        img_tr_load(bfr, tbc0, tbc1, ks);
         asm volatile("s_waitcnt lgkmcnt(0)");
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -589,7 +661,7 @@ __global__ void attn_bwd_delta_kernel(const short* __restrict__ dout,
 // lse/delta are per-lane scalars and dS^T is, as it stands, the B operand
 // of the transposed product dQ^T(d x q) += K^T(d x kv) · dS^T(kv x q)
 // (acc_to_bfrags, natural k order: bit-identical to dQ = dS·K). Q and dO
-// rows live in registers. LDS: K and V panel tiles, double-buffered as in
+// rows live in registers. LDS: K and V tiles in image A, double-buffered as in
 // the forward (loads for tile j+1 issue before the MFMAs on tile j, the
 // LDS writes follow them, one barrier per tile): the first pair is the
 // static 2 x 16 KiB, the second pair the 32 KiB of dynamic LDS
@@ -610,8 +682,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
     short* __restrict__ dq, int B, int H, int Hkv, int S, float scale,
     int causal) {
   constexpr int BQ = 256, BKV = 64;
-  __shared__ short kp[BKV * ATT_D];    // K panels
-  __shared__ short vp[BKV * ATT_D];    // V panels
+  __shared__ short kp[BKV * ATT_D];    // K image
+  __shared__ short vp[BKV * ATT_D];    // V image
 
   const BlockCoord bc = block_coord(S / BQ, H);
   const int qb = S / BQ - 1 - bc.rank;  // most kv tiles first
@@ -649,6 +721,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
   // is (kp, vp), buffer 1 the dynamic pair. Macros as in the forward.
   const int tid = threadIdx.x;
   bf16x8 stg_k[2], stg_v[2];
+  // image addresses (bytes), as in the forward
+  const int stg_off = lds_img::stage16_addr_a(tid);
+  const int rb0 = lds_img::row_base_a(lane, 0);
+  const int rb1 = lds_img::row_base_a(lane, 1);
+  const int trl0 = lds_img::tr_base_a(lane, 0);
+  const int trl1 = lds_img::tr_base_a(lane, 1);
+  const int wid_s = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
 #define MFX_DQ_LOAD(jj)                                                  \
   {                                                                      \
     const short* kb_ = k + kvoff0 + (long long)(jj) * BKV * ATT_D;       \
@@ -662,11 +741,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
 #define MFX_DQ_WRITE(buf)                                                \
   {                                                                      \
     _Pragma("unroll") for (int u = 0; u < 2; ++u) {                      \
-      const int idx_ = u * BLOCK + tid;                                  \
-      const int pel_ = ((idx_ % 16) >> 1) * (BKV * 16) + (idx_ / 16) * 16\
-                       + ((idx_ % 16) & 1) * 8;                          \
-      *(bf16x8*)(((buf) ? dq_kv2 : kp) + pel_) = stg_k[u];               \
-      *(bf16x8*)(((buf) ? dq_kv2 + BKV * ATT_D : vp) + pel_) = stg_v[u]; \
+      const int pel_ = stg_off + u * 8192;                               \
+      *(bf16x8*)((char*)((buf) ? dq_kv2 : kp) + pel_) = stg_k[u];        \
+      *(bf16x8*)((char*)((buf) ? dq_kv2 + BKV * ATT_D : vp) + pel_) =    \
+          stg_v[u];                                                      \
     }                                                                    \
   }
   const int kv_tiles = causal ? (qb * BQ + BQ) / BKV : S / BKV;
@@ -688,27 +766,35 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
       f16f st = (f16f){}, dpt = (f16f){};
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        bf16x8 kf = frag8_panel<BKV>(kpc, t * 32 + l32, s * 16 + hi * 8);
-        bf16x8 vf = frag8_panel<BKV>(vpc, t * 32 + l32, s * 16 + hi * 8);
+        bf16x8 kf = img_row_frag(kpc, rb0, rb1, t, s);
+        bf16x8 vf = img_row_frag(vpc, rb0, rb1, t, s);
         st = mfma32(kf, q_reg[s], st);
         dpt = mfma32(vf, do_reg[s], dpt);
       }
-      // dS = P * (dP - delta) * scale, P = exp(S*scale - lse), causal
+      // dS = P * (dP - delta) * scale, P = exp(S*scale - lse), causal.
+      // The mask sits behind a wave-uniform (scalar) branch: only a
+      // sub-tile whose last key lies above the wave's first q row can
+      // lose an element.
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int kvg = j * BKV + t * 32 + c_row(r, hi);
-        float p = 0.f;
-        if (!causal || kvg <= my_qrow)
-          p = __expf(st[r] * scale - my_lse);
-        st[r] = p * (dpt[r] - my_del) * scale;
+      for (int r = 0; r < 16; ++r) st[r] = __expf(st[r] * scale - my_lse);
+      if (causal && j * BKV + t * 32 + 31 > qb * BQ + wid_s * 32) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kvg = j * BKV + t * 32 + c_row(r, hi);
+          if (kvg > my_qrow) st[r] = 0.f;
+        }
       }
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        st[r] = st[r] * (dpt[r] - my_del) * scale;
       // dQ^T(128d x 32q) += K^T(128d x 32kv) @ dS^T(32kv x 32q)
       bf16x8 pb[2];
       acc_to_bfrags(st, pb);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         BFrag bfr[4];
-        tr_load_bfrags<BKV>(bfr, kpc, t * 32 + ks * 16, lane, hi);
+        img_tr_load(bfr, lds_addr(kpc) + trl0, lds_addr(kpc) + trl1,
+                    t * 2 + ks);
         asm volatile("s_waitcnt lgkmcnt(0)");
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -739,7 +825,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
 // writes FP32 PARTIALS laid out [B, H, S, D]; dkdv_reduce_kernel sums
 // the G partials per kv head and converts to bf16 — numerically
 // identical to the old in-register fp32 accumulation across g. 8 waves
-// x 32 kv rows. LDS: Q and dO panel tiles (2 x 16 KiB) + 64 lse + 64
+// x 32 kv rows. LDS: Q and dO tiles in image A (2 x 16 KiB) + 64 lse + 64
 // delta floats = 33280 bytes.
 //
 // KEY ON THE LANE. S = Q·K^T and dP = dO·V^T come out as C[q][kv]: the
@@ -768,7 +854,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_v2_kernel(
 //
 // Code generation here is fragile (register limit): the coordinates, the
 // transposed-read addressing and the epilogue stay open-coded rather than
-// going through wave_coord() / tr_load_bfrags / store_acc_tile.
+// going through wave_coord() / img_tr_load / store_acc_tile.
 
 // Store a wave's transposed accumulators (acc[n][r] = X[kv = l32][d =
 // n*32 + c_row(r, hi)]) as 32 rows of a row-major [rows][128] fp32 array:
@@ -808,8 +894,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
     float* __restrict__ dk_part, float* __restrict__ dv_part,
     int B, int H, int Hkv, int S, float scale, int causal) {
   constexpr int BKVB = 256, BQ2 = 64;
-  __shared__ short qp[BQ2 * ATT_D];    // Q panels
-  __shared__ short dop[BQ2 * ATT_D];   // dO panels
+  // Q and dO tiles in image A, one array so that a transposed read
+  // reaches either tile from one lane base by an immediate
+  __shared__ short qdo[2 * BQ2 * ATT_D];
+  short* const qp = qdo;                  // Q image
+  short* const dop = qdo + BQ2 * ATT_D;   // dO image
   __shared__ float lse_s[BQ2];
   __shared__ float del_s[BQ2];
 
@@ -855,6 +944,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
     acc_dv[n] = (f16f){};
   }
 
+  // image addresses (bytes): the lane's row-read bases and its
+  // transposed-read bases as LDS addresses into qp; dop lies DOP_REL
+  // bytes from qp
+  const int rb0 = lds_img::row_base_a(lane, 0);
+  const int rb1 = lds_img::row_base_a(lane, 1);
+  const unsigned int tb0 = lds_addr(qp) + lds_img::tr_base_a(lane, 0);
+  const unsigned int tb1 = lds_addr(qp) + lds_img::tr_base_a(lane, 1);
+  constexpr int DOP_REL = BQ2 * ATT_D * 2;
+  // scalar copy of the wave index for the wave-uniform mask branch
+  const int wid_s = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
+
   const long long hoff = ((long long)b * H + h) * S;
   const int jq0 = causal ? (kvb * BKVB) / BQ2 : 0;
   const int nq = S / BQ2;
@@ -862,8 +962,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
     __syncthreads();
     const short* qsrc = q + (hoff + (long long)jq * BQ2) * ATT_D;
     const short* dsrc = dout + (hoff + (long long)jq * BQ2) * ATT_D;
-    stage_panel<BQ2, BLOCK>(qp, qsrc, ATT_D);
-    stage_panel<BQ2, BLOCK>(dop, dsrc, ATT_D);
+    stage_image<BQ2, BLOCK>(qp, qsrc, ATT_D);
+    stage_image<BQ2, BLOCK>(dop, dsrc, ATT_D);
     if (threadIdx.x < BQ2) {
       lse_s[threadIdx.x] = lse[hoff + jq * BQ2 + threadIdx.x];
       del_s[threadIdx.x] = delta[hoff + jq * BQ2 + threadIdx.x];
@@ -878,8 +978,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
       f16f st = (f16f){}, dpt = (f16f){};
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        bf16x8 qf = frag8_panel<BQ2>(qp, t * 32 + l32, s * 16 + hi * 8);
-        bf16x8 df = frag8_panel<BQ2>(dop, t * 32 + l32, s * 16 + hi * 8);
+        bf16x8 qf = img_row_frag(qp, rb0, rb1, t, s);
+        bf16x8 df = img_row_frag(dop, rb0, rb1, t, s);
         bf16x8 vf = *(const bf16x8*)(vimg + s * 512);
         st = mfma32(qf, kr[s], st);
         dpt = mfma32(df, vf, dpt);
@@ -889,20 +989,31 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
       // 64 scalar ds_read_b32 per tile (the dq kernel holds its lse in
       // a register). qrl = t*32 + c_row(r, hi), so r = g*4+j walks
       // 4 consecutive floats at t*32 + 8g + 4hi.
+      // The mask is a pass of its own behind a wave-uniform (scalar) branch: only a
+      // sub-tile whose first q row lies below the wave's last key can
+      // lose an element.
+      const bool edge =
+          causal && jq * BQ2 + t * 32 < kvb * BKVB + wid_s * 32 + 31;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int q0l = t * 32 + g * 8 + 4 * hi;
         const f32x4 lv = *(const f32x4*)&lse_s[q0l];
         const f32x4 dl = *(const f32x4*)&del_s[q0l];
+        float p[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          p[j] = __expf(st[g * 4 + j] * scale - lv[j]);
+        if (edge) {
+          asm volatile("");
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (jq * BQ2 + q0l + j < my_kvrow) p[j] = 0.f;
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int r = g * 4 + j;
-          const int qrg = jq * BQ2 + q0l + j;
-          float p = 0.f;
-          if (!causal || qrg >= my_kvrow)
-            p = __expf(st[r] * scale - lv[j]);
-          st[r] = p;
-          dpt[r] = p * (dpt[r] - dl[j]) * scale;
+          st[r] = p[j];
+          dpt[r] = p[j] * (dpt[r] - dl[j]) * scale;
         }
       }
       // dV^T(128d x 32kv) += dO^T(128d x 32q) @ P(32q x 32kv), then
@@ -915,34 +1026,27 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v2_kernel(
       bf16x8 pb[2], pbk[2];
       acc_to_bfrags(st, pb);
       BFrag bfr[2][4];
-      // same addressing as tr_load_bfrags<BQ2> (derivation there); the
-      // fragments serve as the A operand dO^T / Q^T
-      const int tr_lane_off = (((lane >> 2) & 3) * 16) + (lane & 3) * 4;
-      const int tr_panel = ((lane >> 4) & 1) * (BQ2 * 16);
-      const short* g_tile[4] = {dop, dop, qp, qp};
-      int g_q0[4];
-      g_q0[0] = t * 32;
-      g_q0[1] = t * 32 + 16;
-      g_q0[2] = t * 32;
-      g_q0[3] = t * 32 + 16;
+      // image addressing as img_tr_load (open-coded copy: the lane bases
+      // tb0 / tb1 point into qp, group g reads tile dop (DOP_REL further)
+      // for g < 2 and qp after, k-step 2t + (g & 1)); the fragments serve as the A
+      // operand dO^T / Q^T
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
-        const int base = n * 2 * (BQ2 * 16) + tr_panel
-                         + (g_q0[0] + hi * 8) * 16 + tr_lane_off;
-        bfr[0][n].u[0] = tr_read(g_tile[0] + base);
-        bfr[0][n].u[1] = tr_read(g_tile[0] + base + 4 * 16);
+        const int imm = DOP_REL + lds_img::tr_imm_a(2 * t, n);
+        bfr[0][n].u[0] = tr_read_imm(tb0, imm);
+        bfr[0][n].u[1] = tr_read_imm(tb1, imm);
       }
       acc_to_bfrags(dpt, pbk);  // VALU under the first DS group
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int cur = g & 1;
         if (g < 3) {
+          const int rel = (g + 1 < 2) ? DOP_REL : 0;
 #pragma unroll
           for (int n = 0; n < 4; ++n) {
-            const int base = n * 2 * (BQ2 * 16) + tr_panel
-                             + (g_q0[g + 1] + hi * 8) * 16 + tr_lane_off;
-            bfr[cur ^ 1][n].u[0] = tr_read(g_tile[g + 1] + base);
-            bfr[cur ^ 1][n].u[1] = tr_read(g_tile[g + 1] + base + 4 * 16);
+            const int imm = rel + lds_img::tr_imm_a(2 * t + ((g + 1) & 1), n);
+            bfr[cur ^ 1][n].u[0] = tr_read_imm(tb0, imm);
+            bfr[cur ^ 1][n].u[1] = tr_read_imm(tb1, imm);
           }
           asm volatile("s_waitcnt lgkmcnt(8)");
         } else {

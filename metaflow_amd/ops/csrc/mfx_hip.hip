@@ -721,6 +721,23 @@ std::vector<torch::Tensor> dbg_attn_layout(torch::Tensor t,
   return {st, out};
 }
 
+std::vector<torch::Tensor> dbg_attn_image(torch::Tensor t,
+                                          torch::Tensor x) {
+  check_bf16(t, "t");
+  check_bf16(x, "x");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == 64 && t.size(1) == 128,
+              "t must be [64,128]");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == 32 && x.size(1) == 128,
+              "x must be [32,128]");
+  auto f32opts = t.options().dtype(torch::kFloat32);
+  auto st = torch::empty({64, 32}, f32opts);
+  auto out = torch::empty({32, 128}, f32opts);
+  dbg_attn_image_kernel<<<1, 64, 0, cur_stream()>>>(
+      bf(t), bf(x), st.data_ptr<float>(), out.data_ptr<float>());
+  HIP_CHECK_KERNEL();
+  return {st, out};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -770,4 +787,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");
+  m.def("dbg_attn_image", &dbg_attn_image,
+        "train kernels' dual-use LDS image: staging / row-read / "
+        "transposed-read probe");
 }
