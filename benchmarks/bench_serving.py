@@ -4,9 +4,13 @@ varlen flash-decode kernel), hipGraph replay vs eager decode.
 
     python benchmarks/bench_serving.py [--model llama3-8b] [--slots 8]
         [--requests 24] [--prompt 256] [--new 64] [--pages N]
+        [--temperature T] [--top-k K] [--top-p P] [--seed S]
 
 --pages N serves the same request stream from a paged KV cache of N
 64-row pages (ContinuousBatcher(num_pages=N)) instead of dense slots.
+--temperature > 0 samples every request (with the optional --top-k /
+--top-p cuts; request i is seeded --seed + i); the default decodes
+greedily.
 """
 
 import argparse
@@ -32,7 +36,10 @@ def run_one(model, graph, args, device):
     reqs = [batcher.submit(
         [random.randrange(2, 1000) for _ in
          range(random.randrange(args.prompt // 2, args.prompt))],
-        args.new) for _ in range(args.requests)]
+        args.new, temperature=args.temperature, top_k=args.top_k,
+        top_p=args.top_p,
+        seed=None if args.seed is None else args.seed + i)
+        for i in range(args.requests)]
     import torch
 
     torch.cuda.synchronize()
@@ -57,6 +64,13 @@ def main():
     p.add_argument("--pages", type=int, default=None,
                    help="serve from a paged KV cache with this many "
                         "64-row pages (default: dense slots)")
+    p.add_argument("--temperature", type=float, default=0.0,
+                   help="> 0 samples every request (default: greedy)")
+    p.add_argument("--top-k", type=int, default=0)
+    p.add_argument("--top-p", type=float, default=1.0)
+    p.add_argument("--seed", type=int, default=None,
+                   help="request i draws from a generator seeded "
+                        "seed + i (default: from torch's global RNG)")
     args = p.parse_args()
 
     import torch
@@ -80,7 +94,10 @@ def main():
                        "requests": args.requests,
                        "prompt_max": args.prompt, "new": args.new,
                        "prefill_chunk": args.prefill_chunk,
-                       "pages": args.pages},
+                       "pages": args.pages,
+                       "temperature": args.temperature,
+                       "top_k": args.top_k, "top_p": args.top_p,
+                       "seed": args.seed},
         }), flush=True)
 
 

@@ -46,6 +46,10 @@ class ServingFlow(FlowSpec):
         model = LlamaForCausalLM(cfg).to(device).eval()
         batcher = ContinuousBatcher(model, max_batch=4, max_len=256)
         reqs = [batcher.submit(p, n) for p, n in shard]
+        # sampling is per request: one sampled request rides along with
+        # the greedy ones, reproducibly (its own seeded generator)
+        reqs.append(batcher.submit([5, 9, 17, 4], 8, temperature=0.8,
+                                   top_p=0.9, seed=rank))
         t0 = time.time()
         batcher.run()
         dt = time.time() - t0

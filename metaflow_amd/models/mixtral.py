@@ -363,8 +363,9 @@ class MixtralForCausalLM(nn.Module):
         return self.lm_head(self.final_norm(x))
 
     def generate(self, tokens, max_new_tokens, temperature=0.0,
-                 top_k=None):
-        return generate(self, tokens, max_new_tokens, temperature, top_k)
+                 top_k=None, top_p=None, seed=None):
+        return generate(self, tokens, max_new_tokens, temperature, top_k,
+                        top_p, seed)
 
     def num_params(self):
         return sum(p.numel() for p in self.parameters())

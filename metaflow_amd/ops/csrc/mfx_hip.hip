@@ -14,6 +14,7 @@
 #include "paged.hip"
 #include "decode.hip"
 #include "append.hip"
+#include "sampling.hip"
 #include "debug_kernels.hip"
 
 namespace {
@@ -695,6 +696,58 @@ void kv_page_write(torch::Tensor k, torch::Tensor v, torch::Tensor kp,
   HIP_CHECK_KERNEL();
 }
 
+// ------------------------------------------------------------ sampling
+// [B, V] logits (bf16 or fp32, dense last dim, any row stride) -> int64 [B]
+// token ids, every parameter per row and on the device: no host read, one
+// launch (sampling.hip).
+void check_row_vec(const torch::Tensor& t, int B, torch::ScalarType ty,
+                   const char* name, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.dim() == 1 &&
+              t.numel() == B && t.is_contiguous(),
+              name, " must be ", what, " [B] on GPU");
+}
+
+torch::Tensor sample_tokens(torch::Tensor logits, torch::Tensor temperature,
+                            torch::Tensor top_k, torch::Tensor top_p,
+                            torch::Tensor u) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2,
+              "logits must be [B, V] on GPU");
+  const bool is_bf16 = logits.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == torch::kFloat32,
+              "logits must be bf16 or fp32");
+  const long long B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V < (1ll << 30), "sample_tokens needs 1 <= V < 2^30");
+  TORCH_CHECK(V == 1 || logits.stride(1) == 1,
+              "logits must have a dense last dim");
+  TORCH_CHECK(B == 1 || logits.stride(0) >= 0,
+              "logits row stride must not be negative");
+  check_row_vec(temperature, (int)B, torch::kFloat32, "temperature", "fp32");
+  check_row_vec(top_k, (int)B, torch::kInt32, "top_k", "int32");
+  check_row_vec(top_p, (int)B, torch::kFloat32, "top_p", "fp32");
+  check_row_vec(u, (int)B, torch::kFloat32, "u", "fp32");
+  auto out = torch::empty({B}, logits.options().dtype(torch::kInt64));
+  if (B == 0) return out;
+  const long long stride = B == 1 ? 0 : logits.stride(0);
+  long long* outp = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
+  // fixed-point scale of a weight: 2^44, less where V weights of 1.0 would
+  // not fit 63 bits
+  int bits = 44;
+  while (bits > 0 && (V >> (63 - bits)) != 0) --bits;
+  const float fix = ldexpf(1.f, bits);
+  if (is_bf16)
+    sample_tokens_kernel<short><<<(int)B, SMP_BLOCK, 0, cur_stream()>>>(
+        bf(logits), stride, (int)V, fix, temperature.data_ptr<float>(),
+        top_k.data_ptr<int>(), top_p.data_ptr<float>(), u.data_ptr<float>(),
+        outp);
+  else
+    sample_tokens_kernel<float><<<(int)B, SMP_BLOCK, 0, cur_stream()>>>(
+        logits.data_ptr<float>(), stride, (int)V, fix,
+        temperature.data_ptr<float>(), top_k.data_ptr<int>(),
+        top_p.data_ptr<float>(), u.data_ptr<float>(), outp);
+  HIP_CHECK_KERNEL();
+  return out;
+}
+
 // ------------------------------------------------------- layout probes
 torch::Tensor dbg_mfma32(torch::Tensor a, torch::Tensor b) {
   auto out = torch::empty({32, 32}, a.options().dtype(torch::kFloat32));
@@ -784,6 +837,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_page_write", &kv_page_write,
         "scatter new K/V rows [B,Hkv,S,128] into the page pool at "
         "pos[b].. through the block table (pos < 0 skips the sequence)");
+  m.def("sample_tokens", &sample_tokens,
+        "fused sampler: logits [B,V] (bf16/fp32) + per-row temperature, "
+        "top_k, top_p, u -> int64 [B] token ids (temperature <= 0 = "
+        "argmax)");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");

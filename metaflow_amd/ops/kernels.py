@@ -738,6 +738,96 @@ def kv_page_write(k, v, k_pages, v_pages, block_table, pos):
             v_pages[page, :, r] = v[b, :, s]
 
 
+# ============================== sampling ===================================
+_FLT_BIG = 3.0e38  # bound on 1/T: a denormal T must not make 0 * inf
+
+
+def sample_dist_ref(logits, temperature, top_k, top_p):
+    """The distribution sample_tokens draws from, in fp32 torch ops:
+    (keep, csum, total) with keep the bool [B, V] kept set, csum the
+    running kept weight in index order and total its last column. Rows
+    with temperature <= 0 (greedy) get an all-False keep. No sort:
+    the top-k threshold is a torch.topk, the top-p threshold a per-row
+    torch.unique over the survivors."""
+    x = logits.float()
+    B, V = x.shape
+    t = temperature.float()
+    sampled = t > 0
+    inv_t = torch.clamp(1.0 / torch.where(sampled, t, torch.ones_like(t)),
+                        max=_FLT_BIG)
+    mx = x.max(dim=-1, keepdim=True).values
+    keep = (x > float("-inf")) & sampled[:, None]
+    w = torch.exp((x - mx) * inv_t[:, None])
+    k = top_k.to(torch.long)
+    k_on = sampled & (k > 0) & (k < V)
+    if bool(k_on.any()):
+        kmax = int(k[k_on].max())
+        vals = torch.topk(x, kmax, dim=-1).values
+        kth = vals.gather(1, (k.clamp(1, kmax) - 1)[:, None])
+        keep &= (x >= kth) | ~k_on[:, None]
+    p = top_p.float()
+    for b in torch.nonzero(sampled & (p < 1)).flatten().tolist():
+        idx = torch.nonzero(keep[b]).flatten()
+        if idx.numel() == 0:
+            continue
+        vals, inv = torch.unique(x[b, idx], return_inverse=True)
+        mass = torch.zeros_like(vals).index_add_(0, inv, w[b, idx])
+        # share carried by x >= v_j, walking the distinct values downward
+        share = mass.flip(0).cumsum(0) / mass.sum()
+        hit = torch.nonzero(share >= p[b]).flatten()
+        j = int(hit[0]) if hit.numel() else vals.numel() - 1
+        keep[b] &= x[b] >= vals.flip(0)[j]
+    w = torch.where(keep, w, torch.zeros_like(w))
+    csum = w.cumsum(dim=-1)
+    return keep, csum, csum[:, -1]
+
+
+def sample_tokens_ref(logits, temperature, top_k, top_p, u):
+    """fp32 reference of sample_tokens, on whatever device the inputs
+    live (it reads parameters on the host; the kernel does not)."""
+    x = logits.float()
+    V = x.size(1)
+    keep, csum, total = sample_dist_ref(logits, temperature, top_k, top_p)
+    hit = keep & (csum > (u.float() * total)[:, None])
+    ar = torch.arange(V, device=x.device)
+    first = torch.where(hit, ar, V).min(dim=-1).values
+    last = torch.where(keep, ar, -1).max(dim=-1).values
+    greedy = x.argmax(dim=-1)
+    out = torch.where(first < V, first, last)
+    out = torch.where(out < 0, greedy, out)
+    return torch.where(temperature.float() > 0, out, greedy)
+
+
+def sample_tokens(logits, temperature, top_k, top_p, u):
+    """One token id per row of ``logits``: int64 [B] on its device.
+
+    logits: [B, V] bf16 or fp32 with a dense last dim and any row stride
+    (``full[:, -1]`` of a [B, S, V] tensor is read in place). Per row b:
+    temperature[b] <= 0 is greedy — argmax, lowest index among equal
+    maxima — and ignores the rest. Otherwise the kept set is the finite
+    entries, cut by top-k where 0 < top_k[b] < V (every logit >= the k-th
+    largest; ties kept) and then by top-p where top_p[b] < 1 (with
+    w = exp((x - max) / T) over the survivors, the distinct logit values
+    from the top down to the first whose cumulative share of the weight
+    reaches top_p; ties kept), and the token is the smallest kept index
+    whose running kept weight, in vocabulary order, exceeds u[b] * W.
+    temperature, top_p, u: fp32 [B]; top_k: int32 [B]; u in [0, 1).
+
+    GPU -> sampling.hip: one launch, nothing read on the host, so the
+    call is hipGraph-capturable and costs the caller one host read for
+    all B ids. CPU -> sample_tokens_ref.
+    """
+    if not logits.is_cuda:
+        return sample_tokens_ref(logits, temperature, top_k, top_p, u)
+    dev = logits.device
+    return hip_ext().sample_tokens(
+        logits,
+        temperature.to(device=dev, dtype=torch.float32).contiguous(),
+        top_k.to(device=dev, dtype=torch.int32).contiguous(),
+        top_p.to(device=dev, dtype=torch.float32).contiguous(),
+        u.to(device=dev, dtype=torch.float32).contiguous())
+
+
 # ================================ adam =====================================
 def adamw_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.95, eps=1e-8,
                weight_decay=0.1, master=None, grad_scale=1.0):

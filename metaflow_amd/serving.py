@@ -23,7 +23,17 @@ The engine never asks which cache it holds: admission, page allocation,
 release and the position of a slot that is not decoding are hooks of
 the cache (models/kv_cache.py).
 
-Greedy decoding is token-exact with ``model.generate`` per request.
+Token selection is per request: ``temperature``, ``top_k``, ``top_p`` and
+``seed`` ride on the Request (defaults: greedy). Every selection site is
+one fused sampler launch over all rows (ops/kernels.py sample_tokens,
+ops/csrc/sampling.hip) and ONE host read of the ids, outside the captured
+decode graph. A request owns a CPU generator seeded with its seed; its
+i-th token consumes the generator's i-th draw, wherever that token is
+emitted, so a request's tokens depend neither on its batch neighbours,
+nor on chunked or whole-prompt prefill, nor on eager or graph decode.
+
+Greedy and sampled decoding are token-exact with ``model.generate`` per
+request (``generate(prompt[None], n, temperature, top_k, top_p, seed)``).
 """
 
 from collections import deque
@@ -32,13 +42,32 @@ from collections import deque
 class Request(object):
     _next_id = 0
 
-    def __init__(self, prompt_tokens, max_new_tokens):
+    def __init__(self, prompt_tokens, max_new_tokens, temperature=0.0,
+                 top_k=0, top_p=1.0, seed=None):
         self.id = Request._next_id
         Request._next_id += 1
         self.prompt = list(prompt_tokens)
         self.max_new = int(max_new_tokens)
+        self.temperature = float(temperature or 0.0)
+        self.top_k = int(top_k or 0)
+        self.top_p = 1.0 if top_p is None else float(top_p)
+        self.seed = seed
+        # a greedy request draws nothing and leaves the default RNG alone
+        self._gen = None
+        if self.temperature > 0:
+            from .models.generate import seeded_generator
+
+            self._gen = seeded_generator(seed)
         self.generated = []
         self.done = False
+
+    def draw(self):
+        """The uniform that selects this request's next token."""
+        if self._gen is None:
+            return 0.0
+        from .models.generate import draw
+
+        return draw(self._gen)
 
 
 class ContinuousBatcher(object):
@@ -95,6 +124,13 @@ class ContinuousBatcher(object):
         self._prefill_done = [0] * max_batch  # prompt tokens cached
         self.queue = deque()
         self._torch = torch
+        # per-slot sampling parameters as the sampler reads them; a slot
+        # that is free or mid-prefill holds temperature 0 (its row of the
+        # decode step is selected greedily and ignored)
+        self._temp_host = [0.0] * max_batch
+        self._topk_host = [0] * max_batch
+        self._topp_host = [1.0] * max_batch
+        self._params_stale = True
         self._graph = None
         if graph is True and not getattr(model, "graph_safe_decode",
                                          False):
@@ -146,10 +182,60 @@ class ContinuousBatcher(object):
         # the paged cache from its capacity, as in the captured step
         return self.model.decode_step(tokens, self.cache, positions)
 
-    def submit(self, prompt_tokens, max_new_tokens):
-        req = Request(prompt_tokens, max_new_tokens)
+    def submit(self, prompt_tokens, max_new_tokens, temperature=0.0,
+               top_k=0, top_p=1.0, seed=None):
+        """Queue a request. Defaults decode greedily; temperature > 0
+        samples with the optional top_k / top_p cuts, reproducibly for a
+        given ``seed`` (None draws one from torch's default generator)."""
+        req = Request(prompt_tokens, max_new_tokens, temperature, top_k,
+                      top_p, seed)
         self.queue.append(req)
         return req
+
+    # ------------------------------------------------------------ selection
+    def _sample(self, rows, temperature, top_k, top_p, u_list):
+        """One sampler launch over ``rows`` [R, V] and one host read:
+        the R token ids as Python ints."""
+        from .ops import kernels as K
+
+        u = self._torch.tensor(u_list, dtype=self._torch.float32,
+                               device=self.device)
+        return K.sample_tokens(rows, temperature, top_k, top_p, u).tolist()
+
+    def _first_token(self, slot, logits):
+        """Emit a request's first token from its prefill logits
+        [1, S, V] and hand the slot to the decode batch."""
+        req = self.slots[slot]
+        # the slot's parameters go live here: the first token reads its
+        # one-row slice of the per-slot tensors, the decode steps the whole
+        self._temp_host[slot] = req.temperature
+        self._topk_host[slot] = req.top_k
+        self._topp_host[slot] = req.top_p
+        self._params_stale = True
+        nxt = self._sample(
+            logits[:, -1],
+            *(t[slot:slot + 1] for t in self._slot_params()),
+            [req.draw()])[0]
+        req.generated.append(nxt)
+        self.positions[slot] = len(req.prompt)
+        self.next_token[slot] = nxt
+        if req.max_new <= 1:
+            self._finish(slot)
+
+    def _slot_params(self):
+        """The per-slot parameter tensors, uploaded again only after a
+        slot changed owner."""
+        if self._params_stale:
+            torch = self._torch
+            dev = self.device
+            self._temp = torch.tensor(self._temp_host,
+                                      dtype=torch.float32, device=dev)
+            self._topk = torch.tensor(self._topk_host, dtype=torch.int32,
+                                      device=dev)
+            self._topp = torch.tensor(self._topp_host,
+                                      dtype=torch.float32, device=dev)
+            self._params_stale = False
+        return self._temp, self._topk, self._topp
 
     # ------------------------------------------------------------- internals
     def _admit(self):
@@ -176,12 +262,7 @@ class ContinuousBatcher(object):
             self.cache.sync()
             with torch.no_grad():
                 logits = self.model(prompt, cache=view)
-            nxt = int(logits[0, -1].float().argmax())
-            req.generated.append(nxt)
-            self.positions[slot] = len(req.prompt)
-            self.next_token[slot] = nxt
-            if req.max_new <= 1:
-                self._finish(slot)
+            self._first_token(slot, logits)
 
     def _prefill_step(self):
         """Advance every mid-prefill slot by one prompt chunk; a slot
@@ -204,12 +285,7 @@ class ContinuousBatcher(object):
             if b < len(req.prompt):
                 continue
             self._views[slot] = None
-            nxt = int(logits[0, -1].float().argmax())
-            req.generated.append(nxt)
-            self.positions[slot] = len(req.prompt)
-            self.next_token[slot] = nxt
-            if req.max_new <= 1:
-                self._finish(slot)
+            self._first_token(slot, logits)
 
     def _finish(self, slot):
         self.cache.release(slot)
@@ -218,6 +294,8 @@ class ContinuousBatcher(object):
         self.positions[slot] = 0
         self._views[slot] = None
         self._prefill_done[slot] = 0
+        self._temp_host[slot] = 0.0
+        self._params_stale = True
 
     def step(self):
         """Admit waiting requests, advance mid-prefill slots by one
@@ -241,14 +319,19 @@ class ContinuousBatcher(object):
             self.cache.ensure(i, self.positions[i] + 1)
             pos_list[i] = self.positions[i]
         self.cache.sync()
-        tokens = torch.zeros(self.max_batch, 1, dtype=torch.long,
-                             device=self.device)
+        # one upload each for the token and the u vector
+        tok_list = [0] * self.max_batch
+        u_list = [0.0] * self.max_batch
         for i in active:
-            tokens[i, 0] = self.next_token[i]
+            tok_list[i] = self.next_token[i]
+            u_list[i] = self.slots[i].draw()
+        tokens = torch.tensor(tok_list, dtype=torch.long,
+                              device=self.device).view(-1, 1)
         logits = self._decode(tokens, pos_list)
+        ids = self._sample(logits[:, -1], *self._slot_params(), u_list)
         for i in active:
             req = self.slots[i]
-            nxt = int(logits[i, -1].float().argmax())
+            nxt = ids[i]
             req.generated.append(nxt)
             self.positions[i] += 1
             self.next_token[i] = nxt
