@@ -1,15 +1,17 @@
 """KV caches of the in-house model family, and which attention kernel
 each cached call runs.
 
-Two cache kinds, one interface with three parts:
+Two cache kinds, one interface: every view has
+``attend(layer_idx, q, k, v, S, scale)``, which writes the new K/V rows
+and attends.
 
-* sequence mode (the models' ``forward(tokens, cache=...)``): the object
-  holds one running ``pos``; ``attend`` writes the S new K/V rows there
-  and attends. A KVCache is used whole (generate, speculation) or
-  through ``slot_view(slot)`` (the serving engine's prefill); a
-  PagedKVCache only through its slot views.
-* batch mode (``decode_step``): ``decode_positions`` + ``decode_attend``,
-  one new row per slot, each slot at its own position.
+* sequence views (the models' ``forward(tokens, cache=...)``) hold one
+  running ``pos`` and write the S new rows there. A KVCache is used
+  whole (generate, speculation) or through ``slot_view(slot)`` (the
+  serving engine's prefill); a PagedKVCache only through its slot views.
+* ``decode_view(positions, device, max_len)`` is the view of one batched
+  ``decode_step``: one new row per slot, each slot at its own position.
+  The model reads the RoPE table rows off its ``rope_rows``.
 * engine hooks (serving.ContinuousBatcher): ``admit``, ``ensure``,
   ``sync``, ``release``, ``idle_position``.
 
@@ -70,22 +72,8 @@ class KVCache(_DenseRows):
         return _DenseRows([t[slot:slot + 1] for t in self.k],
                           [t[slot:slot + 1] for t in self.v])
 
-    def decode_positions(self, positions, device):
-        """Device tensors of one batched decode step: (pos_t, lengths,
-        rope_rows). Every slot writes at positions[b]. No host read."""
-        pos_t = torch.as_tensor(positions, device=device, dtype=torch.long)
-        return pos_t, (pos_t + 1).to(torch.int32), pos_t
-
-    def decode_attend(self, layer_idx, q, k, v, pos_t, lengths, scale,
-                      max_len=None):
-        """One layer of the batched decode step: per-slot scatter of the
-        new row, then the varlen flash-decode over the full allocation."""
-        kc, vc = self.k[layer_idx], self.v[layer_idx]
-        bidx = torch.arange(q.size(0), device=q.device)
-        kc[bidx, :, pos_t] = k[:, :, 0]
-        vc[bidx, :, pos_t] = v[:, :, 0]
-        return K.attn_decode_varlen(q.contiguous(), kc, vc, lengths, scale,
-                                    max_len=max_len)
+    def decode_view(self, positions, device, max_len=None):
+        return _DenseDecodeView(self, positions, device, max_len)
 
     # engine hooks: every slot owns its max_len rows from the start
     def admit(self, slot, n_rows):
@@ -106,6 +94,29 @@ class KVCache(_DenseRows):
         — the following prefill chunk overwrites it, so the cached prefix
         stays intact."""
         return rows_cached
+
+
+class _DenseDecodeView(object):
+    """One batched decode step over a KVCache: every slot writes its new
+    row at positions[b]. Built without a host read."""
+
+    def __init__(self, cache, positions, device, max_len):
+        self.cache = cache
+        self.pos_t = torch.as_tensor(positions, device=device,
+                                     dtype=torch.long)
+        self.lengths = (self.pos_t + 1).to(torch.int32)
+        self.rope_rows = self.pos_t
+        self.max_len = max_len
+
+    def attend(self, layer_idx, q, k, v, S, scale):
+        """Per-slot scatter of the new row, then the varlen flash-decode
+        over the full allocation."""
+        kc, vc = self.cache.k[layer_idx], self.cache.v[layer_idx]
+        bidx = torch.arange(q.size(0), device=q.device)
+        kc[bidx, :, self.pos_t] = k[:, :, 0]
+        vc[bidx, :, self.pos_t] = v[:, :, 0]
+        return K.attn_decode_varlen(q.contiguous(), kc, vc, self.lengths,
+                                    scale, max_len=self.max_len)
 
 
 class PagedKVCache(object):
@@ -196,28 +207,8 @@ class PagedKVCache(object):
     def slot_view(self, slot):
         return PagedSlotView(self, slot)
 
-    def decode_positions(self, positions, device):
-        """Device tensors of one batched decode step: (pos_t, lengths,
-        rope_rows). A position of -1 marks a slot that does not take
-        part: pos_t (int32, the write offsets) keeps the -1 so the write
-        skips it, its length is 0 and its RoPE row is clamped to 0. No
-        host read."""
-        pos_t = torch.as_tensor(positions, device=device, dtype=torch.long)
-        return (pos_t.to(torch.int32), (pos_t + 1).to(torch.int32),
-                pos_t.clamp(min=0))
-
-    def decode_attend(self, layer_idx, q, k, v, pos_t, lengths, scale,
-                      max_len=None):
-        """One layer of the batched decode step: one kv_page_write of
-        every slot's new row, one paged flash-decode. The split count
-        always comes from a capacity (max_len or the cache's), so eager
-        and captured steps launch identical grids."""
-        kp, vp = self.k_pages[layer_idx], self.v_pages[layer_idx]
-        K.kv_page_write(k, v, kp, vp, self.block_table, pos_t)
-        return K.attn_decode_paged(q.contiguous(), kp, vp, self.block_table,
-                                   lengths, scale,
-                                   self.max_len if max_len is None
-                                   else max_len)
+    def decode_view(self, positions, device, max_len=None):
+        return _PagedDecodeView(self, positions, device, max_len)
 
     # engine hooks
     def admit(self, slot, n_rows):
@@ -242,6 +233,32 @@ class PagedKVCache(object):
         """No garbage-row trick here: a slot that is not decoding passes
         -1 (nothing written, length 0)."""
         return -1
+
+
+class _PagedDecodeView(object):
+    """One batched decode step over a PagedKVCache. A position of -1
+    marks a slot that does not take part: pos_t (int32, the write
+    offsets) keeps the -1 so the write skips it, its length is 0 and its
+    RoPE row is clamped to 0. Built without a host read."""
+
+    def __init__(self, paged, positions, device, max_len):
+        self.paged = paged
+        pos_t = torch.as_tensor(positions, device=device, dtype=torch.long)
+        self.pos_t = pos_t.to(torch.int32)
+        self.lengths = (pos_t + 1).to(torch.int32)
+        self.rope_rows = pos_t.clamp(min=0)
+        # the split count always comes from a capacity (max_len or the
+        # cache's), so eager and captured steps launch identical grids
+        self.max_len = paged.max_len if max_len is None else max_len
+
+    def attend(self, layer_idx, q, k, v, S, scale):
+        """One kv_page_write of every slot's new row, one paged
+        flash-decode."""
+        pc = self.paged
+        kp, vp = pc.k_pages[layer_idx], pc.v_pages[layer_idx]
+        K.kv_page_write(k, v, kp, vp, pc.block_table, self.pos_t)
+        return K.attn_decode_paged(q.contiguous(), kp, vp, pc.block_table,
+                                   self.lengths, scale, self.max_len)
 
 
 class PagedSlotView(object):

@@ -84,6 +84,38 @@ class RMSNorm(nn.Module):
         return K.rmsnorm(x, self.weight, self.eps)
 
 
+def rope_rows(x, c, s):
+    """Half-rotation RoPE with a per-BATCH position row: x [B,Hh,1,D],
+    c/s [B, D/2] (each slot's own position — the batched-decode case the
+    positional kernel's single-offset layout can't express)."""
+    B, _hh, _one, D = x.shape
+    half = D // 2
+    c = c.view(B, 1, 1, half).float()
+    s = s.view(B, 1, 1, half).float()
+    xf = x.float()
+    x1, x2 = xf[..., :half], xf[..., half:]
+    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(x.dtype)
+
+
+class _NoCache(object):
+    """Attends over the fresh K/V where there is no cache, through the
+    cache views' ``attend`` signature: flash attention, or the xGMI ring
+    (parallel/ring_attention.py) for a context-parallel group."""
+
+    def __init__(self, cp_group=None):
+        self.cp_group = cp_group
+
+    def attend(self, layer_idx, q, k, v, S, scale):
+        if self.cp_group is None:
+            return K.attention(q, k, v)
+        from ..parallel.ring_attention import ring_attention
+
+        return ring_attention(q, k, v, group=self.cp_group)
+
+
+no_cache = _NoCache()
+
+
 class DecoderLayer(nn.Module):
     """Fused projections: one QKV GEMM (the narrow separate K/V GEMMs are
     inefficient on MFMA) and one gate|up GEMM feeding the fused-layout
@@ -110,84 +142,55 @@ class DecoderLayer(nn.Module):
         self.post_norm = RMSNorm(h, cfg.rms_eps)
         self.gate_up_proj = Lin(h, 2 * cfg.intermediate_size)
         self.down_proj = Lin(cfg.intermediate_size, h)
+        self.scale = 1.0 / math.sqrt(hd)
 
-    def forward(self, res, pending, cos_t, sin_t, cp_group=None,
-                cache=None, layer_idx=0):
-        """Carries (residual_stream, pending_branch): every residual add
-        fuses with the next RMSNorm (K.add_rmsnorm). `pending` is the
-        previous layer's un-added MLP output (None for layer 0). With
-        cp_group set, S is the LOCAL sequence shard and attention runs
-        the xGMI ring (parallel/ring_attention.py)."""
+    def _block(self, res, pending, rope_qkv, cos, sin, view, layer_idx):
+        """The layer body. Carries (residual_stream, pending_branch):
+        every residual add fuses with the next RMSNorm (K.add_rmsnorm).
+        `pending` is the previous layer's un-added MLP output (None for
+        layer 0). ``rope_qkv(qkv, cos, sin, nq, nkv)`` gives the roped
+        q, k, v in [B,H,S,D]; ``view`` attends."""
         cfg = self.cfg
         B, S, _ = res.shape
         hd = cfg.head_dim
-        nq, nkv = cfg.num_heads, cfg.num_kv_heads
+        nq = cfg.num_heads
         res, y = K.add_rmsnorm(res, pending, self.input_norm.weight,
                                self.input_norm.eps)
-        qkv = self.qkv_proj(y)
-        # one fused kernel: QKV split + bhsd transpose + RoPE
-        q, k, v = K.rope_qkv(qkv, cos_t, sin_t, nq, nkv)
-        if cache is not None:
-            o = cache.attend(layer_idx, q, k, v, S, 1.0 / math.sqrt(hd))
-        elif cp_group is not None:
-            from ..parallel.ring_attention import ring_attention
-
-            o = ring_attention(q, k, v, group=cp_group)
-        else:
-            o = K.attention(q, k, v)
+        q, k, v = rope_qkv(self.qkv_proj(y), cos, sin, nq, cfg.num_kv_heads)
+        o = view.attend(layer_idx, q, k, v, S, self.scale)
         o = o.transpose(1, 2).reshape(B, S, nq * hd)
-
         res, y = K.add_rmsnorm(res, self.o_proj(o), self.post_norm.weight,
                                self.post_norm.eps)
         pending = self.down_proj(K.swiglu_fused(self.gate_up_proj(y)))
         return res, pending
 
-    def decode_step(self, res, pending, c_rows, s_rows, cache, layer_idx,
-                    pos_t, lengths, max_len=None):
-        """Continuous-batching decode: one new token per slot, each at
-        its OWN cache position (pos_t [B]); the attention is the varlen
-        flash-decode kernel over the full cache allocation."""
-        cfg = self.cfg
-        B = res.size(0)
-        hd = cfg.head_dim
-        nq, nkv = cfg.num_heads, cfg.num_kv_heads
-        res, y = K.add_rmsnorm(res, pending, self.input_norm.weight,
-                               self.input_norm.eps)
-        qkv = self.qkv_proj(y)
+    def _rope_qkv_rows(self, qkv, c_rows, s_rows, nq, nkv):
+        """K.rope_qkv's counterpart for the batched decode step: qkv
+        [B, 1, (nq+2*nkv)*hd] as heads [B, H, 1, hd], q and k rotated by
+        each slot's own table row."""
+        hd = self.cfg.head_dim
         q, k, v = qkv.split([nq * hd, nkv * hd, nkv * hd], dim=-1)
-        q = q.view(B, 1, nq, hd).transpose(1, 2)     # [B, nq, 1, hd]
-        k = k.view(B, 1, nkv, hd).transpose(1, 2)
-        v = v.view(B, 1, nkv, hd).transpose(1, 2)
-        q = _rope_rows(q, c_rows, s_rows)
-        k = _rope_rows(k, c_rows, s_rows)
-        o = cache.decode_attend(layer_idx, q, k, v, pos_t, lengths,
-                                1.0 / math.sqrt(hd), max_len)
-        o = o.transpose(1, 2).reshape(B, 1, nq * hd)
-        res, y = K.add_rmsnorm(res, self.o_proj(o), self.post_norm.weight,
-                               self.post_norm.eps)
-        pending = self.down_proj(K.swiglu_fused(self.gate_up_proj(y)))
-        return res, pending
+        q = q.view(-1, 1, nq, hd).transpose(1, 2)
+        k = k.view(-1, 1, nkv, hd).transpose(1, 2)
+        v = v.view(-1, 1, nkv, hd).transpose(1, 2)
+        return rope_rows(q, c_rows, s_rows), rope_rows(k, c_rows, s_rows), v
 
+    def forward(self, res, pending, cos_t, sin_t, cp_group=None,
+                cache=None, layer_idx=0):
+        """One fused kernel does the QKV split, the bhsd transpose and
+        RoPE. With cp_group set, S is the LOCAL sequence shard and
+        attention runs the xGMI ring."""
+        if cache is None:
+            cache = no_cache if cp_group is None else _NoCache(cp_group)
+        return self._block(res, pending, K.rope_qkv, cos_t, sin_t, cache,
+                           layer_idx)
 
-def _rope_rows(x, c, s):
-    """Half-rotation RoPE with a per-BATCH position row: x [B,Hh,1,D],
-    c/s [B, D/2] (each slot's own position — the batched-decode case the
-    positional kernel's single-offset layout can't express)."""
-    B, _hh, _one, D = x.shape
-    half = D // 2
-    c = c.view(B, 1, 1, half).float()
-    s = s.view(B, 1, 1, half).float()
-    xf = x.float()
-    x1, x2 = xf[..., :half], xf[..., half:]
-    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(x.dtype)
-
-
-def _attn_with_cache(q, k_all, v_all, scale, pos):
-    """Alias of K.attn_append_ref with no caller left in the tree. It
-    stays for one revision because the previous revision of
-    tests/test_attn_append.py imports it at module level, and that
-    suite has to keep running against this tree; delete it next."""
-    return K.attn_append_ref(q, k_all, v_all, pos, scale)
+    def decode_step(self, res, pending, c_rows, s_rows, view, layer_idx):
+        """Continuous-batching decode: one new token per slot, each at
+        its OWN cache position; ``view`` is the cache's decode_view of
+        this step (models/kv_cache.py)."""
+        return self._block(res, pending, self._rope_qkv_rows, c_rows,
+                           s_rows, view, layer_idx)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -287,16 +290,14 @@ class LlamaForCausalLM(nn.Module):
         host reads and is hipGraph-capturable: the serving engine
         captures it once and replays per token (decode is launch-bound;
         see serving.ContinuousBatcher(graph=True))."""
-        pos_t, lengths, rope_rows = cache.decode_positions(positions,
-                                                           tokens.device)
-        c_rows = self.cos_t[rope_rows]
-        s_rows = self.sin_t[rope_rows]
+        view = cache.decode_view(positions, tokens.device, max_len)
+        c_rows = self.cos_t[view.rope_rows]
+        s_rows = self.sin_t[view.rope_rows]
         res = self.embed(tokens)
         pending = None
         for li, layer in enumerate(self.layers):
             res, pending = layer.decode_step(res, pending, c_rows,
-                                             s_rows, cache, li, pos_t,
-                                             lengths, max_len=max_len)
+                                             s_rows, view, li)
         _, x = K.add_rmsnorm(res, pending, self.final_norm.weight,
                              self.final_norm.eps)
         return self.lm_head(x)

@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from ..ops import kernels as K
 from .generate import generate
-from .llama import Linear, RMSNorm, _rope_rows
+from .llama import Linear, RMSNorm, no_cache, rope_rows
 
 
 @dataclass
@@ -257,50 +257,45 @@ class MixtralDecoderLayer(nn.Module):
         self.post_norm = RMSNorm(h, cfg.rms_eps)
         self.moe = MoELayer(cfg, ep_group)
 
-    def forward(self, x, cos_t, sin_t, cache=None, layer_idx=0):
+    def _block(self, x, heads, cos, sin, view, layer_idx):
+        """The layer body. ``heads(y, cos, sin)`` projects the normed
+        input to the roped q, k, v in [B,H,S,D]; ``view`` attends."""
         cfg = self.cfg
         B, S, _ = x.shape
-        res = x
-        y = self.input_norm(x)
-        q = K.rope(self.q_proj(y).view(B, S, cfg.num_heads, cfg.head_dim),
-                   cos_t, sin_t).transpose(1, 2)
-        kk = K.rope(self.k_proj(y).view(B, S, cfg.num_kv_heads,
-                                        cfg.head_dim),
-                    cos_t, sin_t).transpose(1, 2)
-        v = self.v_proj(y).view(B, S, cfg.num_kv_heads,
-                                cfg.head_dim).transpose(1, 2)
-        if cache is not None:
-            o = cache.attend(layer_idx, q, kk, v, S,
-                             1.0 / math.sqrt(cfg.head_dim))
-        else:
-            o = K.attention(q, kk, v)
+        q, k, v = heads(self.input_norm(x), cos, sin)
+        o = view.attend(layer_idx, q, k, v, S, 1.0 / math.sqrt(cfg.head_dim))
         o = o.transpose(1, 2).reshape(B, S, cfg.num_heads * cfg.head_dim)
-        x = res + self.o_proj(o)
-        x = x + self.moe(self.post_norm(x))
-        return x
+        x = x + self.o_proj(o)
+        return x + self.moe(self.post_norm(x))
 
-
-    def decode_step(self, x, c_rows, s_rows, cache, layer_idx, pos_t,
-                    lengths, max_len=None):
-        """Continuous-batching decode for the MoE layer: per-slot cache
-        scatter + varlen flash-decode; experts route per decoded
-        token."""
+    def _seq_heads(self, y, cos_t, sin_t):
         cfg = self.cfg
-        B = x.size(0)
+        B, S, _ = y.shape
         hd = cfg.head_dim
-        res = x
-        y = self.input_norm(x)
-        q = self.q_proj(y).view(B, 1, cfg.num_heads, hd).transpose(1, 2)
-        k = self.k_proj(y).view(B, 1, cfg.num_kv_heads, hd).transpose(1, 2)
-        v = self.v_proj(y).view(B, 1, cfg.num_kv_heads, hd).transpose(1, 2)
-        q = _rope_rows(q, c_rows, s_rows)
-        k = _rope_rows(k, c_rows, s_rows)
-        o = cache.decode_attend(layer_idx, q, k, v, pos_t, lengths,
-                                1.0 / math.sqrt(hd), max_len)
-        o = o.transpose(1, 2).reshape(B, 1, cfg.num_heads * hd)
-        x = res + self.o_proj(o)
-        x = x + self.moe(self.post_norm(x))
-        return x
+        q = K.rope(self.q_proj(y).view(B, S, cfg.num_heads, hd),
+                   cos_t, sin_t).transpose(1, 2)
+        k = K.rope(self.k_proj(y).view(B, S, cfg.num_kv_heads, hd),
+                   cos_t, sin_t).transpose(1, 2)
+        v = self.v_proj(y).view(B, S, cfg.num_kv_heads, hd)
+        return q, k, v.transpose(1, 2)
+
+    def _row_heads(self, y, c_rows, s_rows):
+        B, hd = y.size(0), self.cfg.head_dim
+        q = self.q_proj(y).view(B, 1, -1, hd).transpose(1, 2)
+        k = self.k_proj(y).view(B, 1, -1, hd).transpose(1, 2)
+        v = self.v_proj(y).view(B, 1, -1, hd).transpose(1, 2)
+        return rope_rows(q, c_rows, s_rows), rope_rows(k, c_rows, s_rows), v
+
+    def forward(self, x, cos_t, sin_t, cache=None, layer_idx=0):
+        return self._block(x, self._seq_heads, cos_t, sin_t,
+                           no_cache if cache is None else cache, layer_idx)
+
+    def decode_step(self, x, c_rows, s_rows, view, layer_idx):
+        """Continuous-batching decode for the MoE layer: ``view`` is the
+        cache's decode_view of this step; experts route per decoded
+        token."""
+        return self._block(x, self._row_heads, c_rows, s_rows, view,
+                           layer_idx)
 
 
 class MixtralForCausalLM(nn.Module):
@@ -352,14 +347,12 @@ class MixtralForCausalLM(nn.Module):
         MoE router's token dispatch is shape-dynamic — so the serving
         engine keeps Mixtral on the eager decode path
         (graph_safe_decode stays False)."""
-        pos_t, lengths, rope_rows = cache.decode_positions(positions,
-                                                           tokens.device)
-        c_rows = self.cos_t[rope_rows]
-        s_rows = self.sin_t[rope_rows]
+        view = cache.decode_view(positions, tokens.device, max_len)
+        c_rows = self.cos_t[view.rope_rows]
+        s_rows = self.sin_t[view.rope_rows]
         x = self.embed(tokens)
         for li, layer in enumerate(self.layers):
-            x = layer.decode_step(x, c_rows, s_rows, cache, li, pos_t,
-                                  lengths, max_len=max_len)
+            x = layer.decode_step(x, c_rows, s_rows, view, li)
         return self.lm_head(self.final_norm(x))
 
     def generate(self, tokens, max_new_tokens, temperature=0.0,

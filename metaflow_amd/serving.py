@@ -21,7 +21,9 @@ our own kernels — no reference counterpart, SURVEY §2.4 note):
 
 The engine never asks which cache it holds: admission, page allocation,
 release and the position of a slot that is not decoding are hooks of
-the cache (models/kv_cache.py).
+the cache (models/kv_cache.py). What the engine knows about an occupied
+slot is one record in ``slots`` (None: free); a whole-prompt prefill is
+a chunked one whose chunk is the prompt.
 
 Token selection is per request: ``temperature``, ``top_k``, ``top_p`` and
 ``seed`` ride on the Request (defaults: greedy). Every selection site is
@@ -70,6 +72,24 @@ class Request(object):
         return draw(self._gen)
 
 
+class _Slot(object):
+    """One occupancy of a cache slot, from admission to ``_finish``."""
+
+    def __init__(self, req, view):
+        self.req = req
+        self.view = view     # cache view while prefilling, None once decoding
+        # rows cached. While ``view`` is set these are the prompt tokens
+        # prefilled so far; once it is None, the cache position of the
+        # token the next decode step feeds
+        self.pos = 0
+        self.next_token = 0  # token to feed next step
+
+
+#: what a slot that is free or mid-prefill shows the sampler: its row of
+#: the decode step is selected greedily and ignored
+_GREEDY = (0.0, 0, 1.0)
+
+
 class ContinuousBatcher(object):
     def __init__(self, model, max_batch=8, max_len=2048, graph="auto",
                  prefill_chunk=None, num_pages=None):
@@ -84,9 +104,9 @@ class ContinuousBatcher(object):
         newly admitted request prefills at most this many prompt tokens
         per step() instead of all at once, so active slots keep
         decoding every step instead of stalling behind a monolithic
-        prefill (a slot mid-prefill sits at cache length
-        positions[slot] and its decode row is masked by the varlen
-        kernel's per-slot lengths). None = whole-prompt prefill at
+        prefill (a slot mid-prefill points at the cache's idle position
+        for the rows it has cached, so its decode row disturbs
+        nothing). None = whole-prompt prefill at
         admission (lowest total latency when prompts are short).
 
         num_pages: None keeps the dense cache (max_len rows reserved per
@@ -116,21 +136,11 @@ class ContinuousBatcher(object):
         else:
             self.cache = KVCache(model.cfg, max_batch, max_len, device,
                                  dtype=model.embed.weight.dtype)
-        self.positions = [0] * max_batch    # cached tokens per slot
-        self.slots = [None] * max_batch     # Request or None
-        self.next_token = [0] * max_batch   # token to feed next step
+        self.slots = [None] * max_batch     # _Slot, or None when free
         self.prefill_chunk = prefill_chunk
-        self._views = [None] * max_batch    # slot view while prefilling
-        self._prefill_done = [0] * max_batch  # prompt tokens cached
         self.queue = deque()
         self._torch = torch
-        # per-slot sampling parameters as the sampler reads them; a slot
-        # that is free or mid-prefill holds temperature 0 (its row of the
-        # decode step is selected greedily and ignored)
-        self._temp_host = [0.0] * max_batch
-        self._topk_host = [0] * max_batch
-        self._topp_host = [1.0] * max_batch
-        self._params_stale = True
+        self._params_stale = True  # _slot_params() has to upload again
         self._graph = None
         if graph is True and not getattr(model, "graph_safe_decode",
                                          False):
@@ -202,44 +212,33 @@ class ContinuousBatcher(object):
                                device=self.device)
         return K.sample_tokens(rows, temperature, top_k, top_p, u).tolist()
 
-    def _first_token(self, slot, logits):
-        """Emit a request's first token from its prefill logits
-        [1, S, V] and hand the slot to the decode batch."""
-        req = self.slots[slot]
-        # the slot's parameters go live here: the first token reads its
-        # one-row slice of the per-slot tensors, the decode steps the whole
-        self._temp_host[slot] = req.temperature
-        self._topk_host[slot] = req.top_k
-        self._topp_host[slot] = req.top_p
-        self._params_stale = True
-        nxt = self._sample(
-            logits[:, -1],
-            *(t[slot:slot + 1] for t in self._slot_params()),
-            [req.draw()])[0]
-        req.generated.append(nxt)
-        self.positions[slot] = len(req.prompt)
-        self.next_token[slot] = nxt
-        if req.max_new <= 1:
-            self._finish(slot)
-
     def _slot_params(self):
-        """The per-slot parameter tensors, uploaded again only after a
-        slot changed owner."""
+        """The per-slot parameter tensors as the sampler reads them: a
+        decoding slot shows its request's parameters. Uploaded again only
+        after a slot changed owner or phase."""
         if self._params_stale:
             torch = self._torch
             dev = self.device
-            self._temp = torch.tensor(self._temp_host,
-                                      dtype=torch.float32, device=dev)
-            self._topk = torch.tensor(self._topk_host, dtype=torch.int32,
-                                      device=dev)
-            self._topp = torch.tensor(self._topp_host,
-                                      dtype=torch.float32, device=dev)
+            temp, topk, topp = zip(*(
+                (s.req.temperature, s.req.top_k, s.req.top_p)
+                if s is not None and s.view is None else _GREEDY
+                for s in self.slots))
+            self._temp = torch.tensor(temp, dtype=torch.float32, device=dev)
+            self._topk = torch.tensor(topk, dtype=torch.int32, device=dev)
+            self._topp = torch.tensor(topp, dtype=torch.float32, device=dev)
             self._params_stale = False
         return self._temp, self._topk, self._topp
 
+    def _position(self, s):
+        """Where slot record ``s`` (None: free) points in the batched
+        step: a decoding slot at the row it is about to write, any other
+        at the cache's idle position for the rows it has cached."""
+        if s is None:
+            return self.cache.idle_position(0)
+        return s.pos if s.view is None else self.cache.idle_position(s.pos)
+
     # ------------------------------------------------------------- internals
     def _admit(self):
-        torch = self._torch
         for slot in range(self.max_batch):
             if self.slots[slot] is not None or not self.queue:
                 continue
@@ -249,52 +248,44 @@ class ContinuousBatcher(object):
             self.queue.popleft()
             assert len(req.prompt) + req.max_new <= self.max_len, \
                 "request longer than the slot capacity"
-            self.slots[slot] = req
-            if self.prefill_chunk is not None:
-                # chunked: cache nothing yet; step() feeds chunks
-                self._views[slot] = self.cache.slot_view(slot)
-                self._prefill_done[slot] = 0
-                self.positions[slot] = 0
-                continue
-            prompt = torch.tensor([req.prompt], device=self.device)
-            view = self.cache.slot_view(slot)
-            self.cache.ensure(slot, len(req.prompt))
-            self.cache.sync()
-            with torch.no_grad():
-                logits = self.model(prompt, cache=view)
-            self._first_token(slot, logits)
+            self.slots[slot] = _Slot(req, self.cache.slot_view(slot))
+            # chunked: cache nothing yet; step() feeds chunks
+            if self.prefill_chunk is None:
+                self._prefill(slot, len(req.prompt))
 
-    def _prefill_step(self):
-        """Advance every mid-prefill slot by one prompt chunk; a slot
-        whose final chunk just ran emits its first token and joins the
-        decode batch next step."""
+    def _prefill(self, slot, n):
+        """Advance a mid-prefill slot by up to ``n`` prompt tokens; once
+        the prompt is cached, emit the request's first token and hand the
+        slot to the decode batch."""
         torch = self._torch
-        for slot in range(self.max_batch):
-            view = self._views[slot]
-            if view is None:
-                continue
-            req = self.slots[slot]
-            a = self._prefill_done[slot]
-            b = min(a + self.prefill_chunk, len(req.prompt))
-            chunk = torch.tensor([req.prompt[a:b]], device=self.device)
-            self.cache.ensure(slot, b)
-            self.cache.sync()
-            with torch.no_grad():
-                logits = self.model(chunk, cache=view)
-            self._prefill_done[slot] = b
-            if b < len(req.prompt):
-                continue
-            self._views[slot] = None
-            self._first_token(slot, logits)
+        s = self.slots[slot]
+        req = s.req
+        end = min(s.pos + n, len(req.prompt))
+        chunk = torch.tensor([req.prompt[s.pos:end]], device=self.device)
+        self.cache.ensure(slot, end)
+        self.cache.sync()
+        with torch.no_grad():
+            logits = self.model(chunk, cache=s.view)
+        s.pos = end
+        if end < len(req.prompt):
+            return
+        # the slot's parameters go live here: the first token reads its
+        # one-row slice of the per-slot tensors, the decode steps the whole
+        s.view = None
+        self._params_stale = True
+        nxt = self._sample(
+            logits[:, -1],
+            *(t[slot:slot + 1] for t in self._slot_params()),
+            [req.draw()])[0]
+        req.generated.append(nxt)
+        s.next_token = nxt
+        if req.max_new <= 1:
+            self._finish(slot)
 
     def _finish(self, slot):
         self.cache.release(slot)
-        self.slots[slot].done = True
+        self.slots[slot].req.done = True
         self.slots[slot] = None
-        self.positions[slot] = 0
-        self._views[slot] = None
-        self._prefill_done[slot] = 0
-        self._temp_host[slot] = 0.0
         self._params_stale = True
 
     def step(self):
@@ -304,38 +295,34 @@ class ContinuousBatcher(object):
         torch = self._torch
         self._admit()
         if self.prefill_chunk is not None:
-            self._prefill_step()
-        active = [i for i, r in enumerate(self.slots) if r is not None
-                  and self._views[i] is None]
+            for i, s in enumerate(self.slots):
+                if s is not None and s.view is not None:
+                    self._prefill(i, self.prefill_chunk)
+        active = [i for i, s in enumerate(self.slots)
+                  if s is not None and s.view is None]
         if not active:
             return 0
-        # every slot starts at the cache's idle position for the rows it
-        # has cached: _prefill_done for a mid-prefill slot, and 0 for a
-        # free one (_finish resets _prefill_done along with positions).
-        # A decoding slot gets the page of the row it is about to write
-        pos_list = [self.cache.idle_position(n)
-                    for n in self._prefill_done]
+        pos_list = [self._position(s) for s in self.slots]
+        # a decoding slot gets the page of the row it is about to write
         for i in active:
-            self.cache.ensure(i, self.positions[i] + 1)
-            pos_list[i] = self.positions[i]
+            self.cache.ensure(i, pos_list[i] + 1)
         self.cache.sync()
         # one upload each for the token and the u vector
         tok_list = [0] * self.max_batch
         u_list = [0.0] * self.max_batch
         for i in active:
-            tok_list[i] = self.next_token[i]
-            u_list[i] = self.slots[i].draw()
+            tok_list[i] = self.slots[i].next_token
+            u_list[i] = self.slots[i].req.draw()
         tokens = torch.tensor(tok_list, dtype=torch.long,
                               device=self.device).view(-1, 1)
         logits = self._decode(tokens, pos_list)
         ids = self._sample(logits[:, -1], *self._slot_params(), u_list)
         for i in active:
-            req = self.slots[i]
-            nxt = ids[i]
-            req.generated.append(nxt)
-            self.positions[i] += 1
-            self.next_token[i] = nxt
-            if len(req.generated) >= req.max_new:
+            s = self.slots[i]
+            s.req.generated.append(ids[i])
+            s.pos += 1
+            s.next_token = ids[i]
+            if len(s.req.generated) >= s.req.max_new:
                 self._finish(i)
         return len(active)
 
