@@ -3,10 +3,17 @@
 
     python benchmarks/bench_decode.py [--model llama3-8b] [--batch 8]
         [--prompt 512] [--new 128]
+    python benchmarks/bench_decode.py --model mixtral-tiny --fused-moe
 
 Measures prefill time and per-token decode rate separately. The decode
 attention runs the split-K flash-decode kernel (ops/csrc/decode.hip)
 straight over the cache allocation; prefill runs the flash fwd kernel.
+
+--fused-moe (mixtral-tiny) measures the serving decode step instead: the
+continuous batcher over --batch requests of --new tokens with the eager MoE
+block, with the fused block (cfg.fused_moe_decode, ops/csrc/moe.hip) run
+eagerly, and with the fused block replayed from a captured hipGraph, which
+only the fused block allows.
 """
 
 import argparse
@@ -19,6 +26,64 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(
     os.path.abspath(__file__))))
 
 
+def fused_moe_serving(args, device):
+    """Tokens/s of ContinuousBatcher.run() on tiny Mixtral, three ways, 3
+    alternating rounds, every run listed."""
+    import torch
+
+    from metaflow_amd.models.mixtral import (
+        MixtralConfig,
+        MixtralForCausalLM,
+    )
+    from metaflow_amd.serving import ContinuousBatcher
+
+    assert device.type == "cuda", "--fused-moe measures on a GPU"
+    cfg = MixtralConfig.tiny()
+    torch.manual_seed(0)
+    with torch.device(device):
+        model = MixtralForCausalLM(cfg)
+    model.eval()
+    prompt_len = min(args.prompt, 16)
+    g = torch.Generator().manual_seed(0)
+    prompts = [torch.randint(0, cfg.vocab_size, (prompt_len,),
+                             generator=g).tolist()
+               for _ in range(args.batch)]
+    modes = {"eager_moe": (False, False), "fused_moe": (True, False),
+             "fused_moe_graph": (True, True)}
+    runs = {name: [] for name in modes}
+    tokens = {}
+    for rnd in range(4):  # round 0 warms up
+        for name, (fused, graph) in modes.items():
+            cfg.fused_moe_decode = fused
+            b = ContinuousBatcher(model, max_batch=args.batch,
+                                  max_len=prompt_len + args.new + 64,
+                                  graph=graph)
+            reqs = [b.submit(pr, args.new) for pr in prompts]
+            torch.cuda.synchronize()
+            t0 = time.time()
+            out = b.run()
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+            tokens[name] = [out[r.id] for r in reqs]
+            if rnd:
+                runs[name].append(round(args.batch * args.new / dt, 1))
+    cfg.fused_moe_decode = False
+    print(json.dumps({
+        "metric": "serving decode tokens/sec (prefill of %d tokens "
+                  "included)" % prompt_len,
+        "unit": "tokens/s", "higher_is_better": True, "runs": runs,
+        # the fused block rounds less than the eager one, so greedy tokens
+        # may part from eager_moe's; replay must reproduce the fused run
+        "fused_same_tokens_as_eager": tokens["fused_moe"] ==
+        tokens["eager_moe"],
+        "graph_same_tokens_as_fused": tokens["fused_moe_graph"] ==
+        tokens["fused_moe"],
+        "config": {"model": args.model, "batch": args.batch,
+                   "prompt": prompt_len, "new": args.new,
+                   "device": str(device)},
+    }), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="llama3-8b",
@@ -26,7 +91,12 @@ def main():
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--prompt", type=int, default=512)
     p.add_argument("--new", type=int, default=128)
+    p.add_argument("--fused-moe", action="store_true",
+                   help="mixtral-tiny: serving decode, eager MoE vs fused "
+                        "MoE (eager and graph replay)")
     args = p.parse_args()
+    if args.fused_moe and args.model != "mixtral-tiny":
+        p.error("--fused-moe needs --model mixtral-tiny")
 
     import torch
 
@@ -38,6 +108,8 @@ def main():
 
     use_gpu = torch.cuda.is_available()
     device = torch.device("cuda", 0) if use_gpu else torch.device("cpu")
+    if args.fused_moe:
+        return fused_moe_serving(args, device)
     factories = {
         "llama3-8b": (LlamaConfig.llama3_8b, LlamaForCausalLM),
         "tiny": (LlamaConfig.tiny, LlamaForCausalLM),

@@ -35,6 +35,9 @@ class MixtralConfig:
     max_seq_len: int = 8192
     rope_theta: float = 1000000.0
     rms_eps: float = 1e-5
+    # decode_step runs the MoE block through the fused device-routed
+    # kernels (ops/csrc/moe.hip): no host read, hipGraph-capturable
+    fused_moe_decode: bool = False
 
     @classmethod
     def mixtral_8x7b(cls):
@@ -243,6 +246,25 @@ class MoELayer(nn.Module):
         out.index_add_(0, token_idx, contrib)
         return out.reshape(B, S, h)
 
+    def decode(self, x):
+        """The block at decode time, inference-only and without EP: the
+        router GEMM, then K.moe_ffn (device routing, grouped expert
+        kernels). Reads nothing back, unlike forward's per-expert counts.
+        The table of weight addresses is cached and rebuilt when a weight
+        has moved (a host-side comparison of data_ptr()s)."""
+        assert self.ep_world == 1, "fused MoE decode has no EP path"
+        B, S, h = x.shape
+        flat = x.reshape(B * S, h)
+        logits = self.router(flat).float()
+        ws = ([e.gate_proj.weight for e in self.local_experts],
+              [e.up_proj.weight for e in self.local_experts],
+              [e.down_proj.weight for e in self.local_experts])
+        table = getattr(self, "_moe_table", None)
+        if table is None or table.ptrs != K.MoeTable.addresses(*ws):
+            table = self._moe_table = K.MoeTable(*ws)
+        out = K.moe_ffn(flat, logits, table, top_k=self.cfg.top_k)
+        return out.reshape(B, S, h)
+
 
 class MixtralDecoderLayer(nn.Module):
     def __init__(self, cfg: MixtralConfig, ep_group=None):
@@ -257,16 +279,17 @@ class MixtralDecoderLayer(nn.Module):
         self.post_norm = RMSNorm(h, cfg.rms_eps)
         self.moe = MoELayer(cfg, ep_group)
 
-    def _block(self, x, heads, cos, sin, view, layer_idx):
+    def _block(self, x, heads, cos, sin, view, layer_idx, moe=None):
         """The layer body. ``heads(y, cos, sin)`` projects the normed
-        input to the roped q, k, v in [B,H,S,D]; ``view`` attends."""
+        input to the roped q, k, v in [B,H,S,D]; ``view`` attends; ``moe``
+        is the MoE block's entry (its forward unless given)."""
         cfg = self.cfg
         B, S, _ = x.shape
         q, k, v = heads(self.input_norm(x), cos, sin)
         o = view.attend(layer_idx, q, k, v, S, 1.0 / math.sqrt(cfg.head_dim))
         o = o.transpose(1, 2).reshape(B, S, cfg.num_heads * cfg.head_dim)
         x = x + self.o_proj(o)
-        return x + self.moe(self.post_norm(x))
+        return x + (moe or self.moe)(self.post_norm(x))
 
     def _seq_heads(self, y, cos_t, sin_t):
         cfg = self.cfg
@@ -293,9 +316,11 @@ class MixtralDecoderLayer(nn.Module):
     def decode_step(self, x, c_rows, s_rows, view, layer_idx):
         """Continuous-batching decode for the MoE layer: ``view`` is the
         cache's decode_view of this step; experts route per decoded
-        token."""
+        token. With cfg.fused_moe_decode (and no expert parallelism) the
+        MoE block runs MoELayer.decode."""
+        fused = self.cfg.fused_moe_decode and self.moe.ep_world == 1
         return self._block(x, self._row_heads, c_rows, s_rows, view,
-                           layer_idx)
+                           layer_idx, self.moe.decode if fused else None)
 
 
 class MixtralForCausalLM(nn.Module):
@@ -314,6 +339,13 @@ class MixtralForCausalLM(nn.Module):
         self.register_buffer("cos_t", cos_t, persistent=False)
         self.register_buffer("sin_t", sin_t, persistent=False)
         self.reset_parameters()
+
+    @property
+    def graph_safe_decode(self):
+        """decode_step reads nothing back from the device exactly when
+        every layer's MoE block takes the fused path."""
+        return self.cfg.fused_moe_decode and all(
+            layer.moe.ep_world == 1 for layer in self.layers)
 
     def reset_parameters(self):
         for p in self.parameters():
@@ -343,10 +375,11 @@ class MixtralForCausalLM(nn.Module):
     def decode_step(self, tokens, cache, positions, max_len=None):
         """One batched decode step for continuous batching (same
         contract as LlamaForCausalLM.decode_step: per-slot cache
-        positions, varlen flash-decode). NOT hipGraph-capturable — the
-        MoE router's token dispatch is shape-dynamic — so the serving
-        engine keeps Mixtral on the eager decode path
-        (graph_safe_decode stays False)."""
+        positions, varlen flash-decode). With the eager MoE block it is
+        NOT hipGraph-capturable — the router's token dispatch is
+        shape-dynamic and read on the host — so the serving engine keeps
+        Mixtral on the eager decode path; with cfg.fused_moe_decode it
+        is (graph_safe_decode)."""
         view = cache.decode_view(positions, tokens.device, max_len)
         c_rows = self.cos_t[view.rope_rows]
         s_rows = self.sin_t[view.rope_rows]

@@ -15,6 +15,7 @@
 #include "decode.hip"
 #include "append.hip"
 #include "sampling.hip"
+#include "moe.hip"
 #include "debug_kernels.hip"
 
 namespace {
@@ -748,6 +749,108 @@ torch::Tensor sample_tokens(torch::Tensor logits, torch::Tensor temperature,
   return out;
 }
 
+// ----------------------------------------------------------------- MoE
+// Decode-time MoE feed-forward (moe.hip). Nothing is read on the host.
+// {expert [T,k] i32, weight [T,k] f32, order [T*k] i32, offset [E+1] i32,
+//  slot [T*k] i32 (the inverse of order)}
+std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t k) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 &&
+              logits.scalar_type() == torch::kFloat32 &&
+              logits.is_contiguous(),
+              "logits must be contiguous fp32 [T, E] on GPU");
+  const long long T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(E >= 1 && E <= MOE_MAX_E, "moe_route needs 1 <= E <= ",
+              MOE_MAX_E, ", got ", E);
+  TORCH_CHECK(k >= 1 && k <= MOE_MAX_K && k <= E,
+              "moe_route needs 1 <= top_k <= min(E, ", MOE_MAX_K, "), got ",
+              k);
+  TORCH_CHECK(T >= 1 && T * k <= MOE_MAX_ENTRIES,
+              "moe_route needs 1 <= T * top_k <= ", MOE_MAX_ENTRIES,
+              ", got T = ", T);
+  auto i32 = logits.options().dtype(torch::kInt32);
+  auto expert = torch::empty({T, k}, i32);
+  auto weight = torch::empty({T, k}, logits.options());
+  auto order = torch::empty({T * k}, i32);
+  auto offset = torch::empty({E + 1}, i32);
+  auto slot = torch::empty({T * k}, i32);
+  moe_route_kernel<<<1, MOE_ROUTE_BLOCK, 0, cur_stream()>>>(
+      logits.data_ptr<float>(), (int)T, (int)E, (int)k,
+      expert.data_ptr<int>(), weight.data_ptr<float>(),
+      order.data_ptr<int>(), offset.data_ptr<int>(), slot.data_ptr<int>());
+  HIP_CHECK_KERNEL();
+  return {expert, weight, order, offset, slot};
+}
+
+// Split-K of the down projection, from shapes alone: enough blocks to
+// cover the chip twice when only min(E, T*k) experts can be active.
+int moe_down_splits(long long E, long long entries, long long hidden,
+                    long long inter) {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
+                hipDeviceGetAttribute(
+                    &cus, hipDeviceAttributeMultiprocessorCount, dev) ==
+                    hipSuccess && cus > 0,
+                "cannot read the CU count");
+  }
+  const long long active = std::min(E, entries) * (hidden / MOE_ROWS);
+  const long long want = (2ll * cus + active - 1) / active;
+  return (int)std::max<long long>(
+      1, std::min<long long>({want, inter / MOE_KC, 16ll}));
+}
+
+// x [T, hidden] bf16, logits [T, E] fp32, tab int64 [3, E] device table of
+// the gate / up / down weight addresses ([inter, hidden] x2, [hidden,
+// inter], bf16, 16-byte aligned) -> out [T, hidden] bf16.
+torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
+                      torch::Tensor tab, int64_t k, int64_t inter,
+                      int64_t splits) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2 && logits.dim() == 2 &&
+              logits.size(0) == x.size(0),
+              "x must be [T, hidden] and logits [T, E]");
+  const long long T = x.size(0), hidden = x.size(1), E = logits.size(1);
+  TORCH_CHECK(hidden % 128 == 0 && inter % 128 == 0 && hidden > 0 &&
+              inter > 0,
+              "moe_ffn needs hidden and inter to be multiples of 128, got ",
+              hidden, " and ", inter);
+  TORCH_CHECK(tab.is_cuda() && tab.scalar_type() == torch::kInt64 &&
+              tab.dim() == 2 && tab.size(0) == 3 && tab.size(1) == E &&
+              tab.is_contiguous(),
+              "tab must be a contiguous int64 [3, E] table on GPU");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
+              "x must be 16-byte aligned");
+  auto r = moe_route(logits, k);
+  const long long entries = T * k;
+  const long long nc = inter / MOE_KC;
+  if (splits <= 0) splits = moe_down_splits(E, entries, hidden, inter);
+  TORCH_CHECK(splits <= nc && splits <= 64,
+              "down_splits must be at most inter / 128 and 64");
+  auto h = torch::empty({entries, inter}, x.options());
+  auto y = torch::empty({splits, entries, hidden},
+                        x.options().dtype(torch::kFloat32));
+  auto out = torch::empty_like(x);
+  const long long* tp =
+      reinterpret_cast<const long long*>(tab.data_ptr<int64_t>());
+  moe_gate_up_kernel<<<dim3(inter / MOE_ROWS, E), MOE_BLOCK, 0,
+                       cur_stream()>>>(
+      bf(x), tp, r[2].data_ptr<int>(), r[3].data_ptr<int>(), bfm(h), (int)E,
+      (int)k, (int)hidden, (int)inter);
+  HIP_CHECK_KERNEL();
+  moe_down_kernel<<<dim3(hidden / MOE_ROWS, E, splits), MOE_BLOCK, 0,
+                    cur_stream()>>>(
+      bf(h), tp, r[3].data_ptr<int>(), y.data_ptr<float>(), (int)E,
+      (int)entries, (int)hidden, (int)inter);
+  HIP_CHECK_KERNEL();
+  moe_combine_kernel<<<dim3((hidden + 1023) / 1024, T), 256, 0,
+                       cur_stream()>>>(
+      y.data_ptr<float>(), r[1].data_ptr<float>(), r[4].data_ptr<int>(),
+      bfm(out), (int)k, (int)splits, (int)entries, (int)hidden);
+  HIP_CHECK_KERNEL();
+  return out;
+}
+
 // ------------------------------------------------------- layout probes
 torch::Tensor dbg_mfma32(torch::Tensor a, torch::Tensor b) {
   auto out = torch::empty({32, 32}, a.options().dtype(torch::kFloat32));
@@ -841,6 +944,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused sampler: logits [B,V] (bf16/fp32) + per-row temperature, "
         "top_k, top_p, u -> int64 [B] token ids (temperature <= 0 = "
         "argmax)");
+  m.def("moe_route", &moe_route,
+        "MoE routing on the device: logits fp32 [T,E], top_k -> expert, "
+        "weight, order, offset, slot");
+  m.def("moe_ffn", &moe_ffn,
+        "decode-time MoE feed-forward: x [T,hidden], logits fp32 [T,E], "
+        "int64 [3,E] weight address table, top_k, inter, down splits "
+        "(<= 0 = from shapes) -> [T,hidden]");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");

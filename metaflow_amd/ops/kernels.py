@@ -828,6 +828,159 @@ def sample_tokens(logits, temperature, top_k, top_p, u):
         u.to(device=dev, dtype=torch.float32).contiguous())
 
 
+# ================================= MoE =====================================
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOP_K = 8
+MOE_MAX_ENTRIES = 2048
+
+
+def _moe_check_route(T, E, top_k):
+    if not 1 <= E <= MOE_MAX_EXPERTS:
+        raise ValueError("moe_route needs 1 <= E <= %d, got %d"
+                         % (MOE_MAX_EXPERTS, E))
+    if not 1 <= top_k <= min(E, MOE_MAX_TOP_K):
+        raise ValueError("moe_route needs 1 <= top_k <= min(E, %d), got %d"
+                         % (MOE_MAX_TOP_K, top_k))
+    if not 1 <= T * top_k <= MOE_MAX_ENTRIES:
+        raise ValueError("moe_route needs 1 <= T * top_k <= %d, got T = %d"
+                         % (MOE_MAX_ENTRIES, T))
+
+
+def _moe_no_grad(*tensors):
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(
+            "the fused MoE path is inference-only: call it under "
+            "torch.no_grad() or with inputs that do not require grad")
+
+
+def moe_route_ref(logits, top_k):
+    """Reference of moe_route in the precision of ``logits`` (fp32, or
+    fp64 when given fp64): (expert [T,k] int32, weight [T,k], order [T*k]
+    int32, offset [E+1] int32). Selection: the k largest logits of a row,
+    the lowest index among equal ones (a stable descending sort); weight:
+    softmax over the selected logits; order: the entries t*k + j grouped by
+    expert, ascending within one; offset: where each expert's run starts."""
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    T, E = x.shape
+    _moe_check_route(T, E, top_k)
+    vals, idx = torch.sort(x, dim=-1, descending=True, stable=True)
+    expert = idx[:, :top_k]
+    weight = torch.softmax(vals[:, :top_k], dim=-1)
+    flat = expert.reshape(-1)
+    order = torch.argsort(flat, stable=True)
+    offset = torch.zeros(E + 1, dtype=torch.long, device=x.device)
+    offset[1:] = torch.bincount(flat, minlength=E).cumsum(0)
+    return (expert.to(torch.int32), weight, order.to(torch.int32),
+            offset.to(torch.int32))
+
+
+def moe_route(logits, top_k):
+    """Top-k routing of [T, E] fp32 router logits, see moe_route_ref.
+
+    GPU -> moe.hip (one small workgroup, no atomics, nothing read on the
+    host). CPU -> moe_route_ref. Inference-only."""
+    _moe_no_grad(logits)
+    if not logits.is_cuda:
+        return moe_route_ref(logits, top_k)
+    _moe_check_route(logits.size(0), logits.size(1), top_k)
+    return tuple(hip_ext().moe_route(logits.float().contiguous(),
+                                     top_k)[:4])
+
+
+class MoeTable(object):
+    """The expert weights of one MoE layer as the kernels take them: an
+    int64 [3, E] device table of the gate / up / down base addresses. The
+    parameters stay where they are; ``ptrs`` is the host copy of the
+    addresses, to compare against when a weight may have moved."""
+
+    def __init__(self, w_gate, w_up, w_down):
+        self.weights = (tuple(w_gate), tuple(w_up), tuple(w_down))
+        E = len(self.weights[0])
+        if E == 0 or any(len(ws) != E for ws in self.weights):
+            raise ValueError("moe_ffn needs E gate, up and down weights")
+        self.inter, self.hidden = self.weights[0][0].shape
+        if self.hidden % 128 or self.inter % 128:
+            raise ValueError(
+                "moe_ffn needs hidden and inter to be multiples of 128, got "
+                "%d and %d" % (self.hidden, self.inter))
+        shapes = ((self.inter, self.hidden),) * 2 + \
+            ((self.hidden, self.inter),)
+        dev = self.weights[0][0].device
+        for ws, shape in zip(self.weights, shapes):
+            for w in ws:
+                if tuple(w.shape) != shape or w.device != dev:
+                    raise ValueError("expert weights must share one device "
+                                     "and be [inter, hidden] (gate, up) and "
+                                     "[hidden, inter] (down)")
+                if dev.type == "cuda" and not (
+                        w.dtype == torch.bfloat16 and w.is_contiguous()
+                        and w.data_ptr() % 16 == 0):
+                    raise ValueError("expert weights must be contiguous "
+                                     "16-byte-aligned bf16 on the GPU")
+        self.ptrs = self.addresses(*self.weights)
+        self.tab = None
+        if dev.type == "cuda":
+            self.tab = torch.tensor(self.ptrs, dtype=torch.int64,
+                                    device=dev).reshape(3, E)
+
+    @staticmethod
+    def addresses(w_gate, w_up, w_down):
+        return tuple(w.data_ptr() for ws in (w_gate, w_up, w_down)
+                     for w in ws)
+
+
+def moe_ffn_ref(x, logits, w_gate, w_up, w_down, top_k,
+                dtype=torch.float32):
+    """Reference MoE feed-forward in ``dtype`` with no intermediate
+    rounding: out[t] = sum_j weight[t, j] * down_e(silu(gate_e x_t) *
+    up_e x_t), e = expert[t, j], routed by moe_route_ref. x [T, hidden],
+    logits [T, E], w_* sequences of E [out, in] weights. Returns ``dtype``."""
+    expert, weight, _, _ = moe_route_ref(logits.to(dtype), top_k)
+    xf = x.to(dtype)
+    out = torch.zeros_like(xf)
+    for e in range(len(w_gate)):
+        coef = (weight * (expert == e)).sum(-1, keepdim=True)
+        g = xf @ w_gate[e].to(dtype).t()
+        u = xf @ w_up[e].to(dtype).t()
+        y = (torch.nn.functional.silu(g) * u) @ w_down[e].to(dtype).t()
+        out += coef * y
+    return out
+
+
+def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
+            down_splits=None):
+    """Decode-time MoE feed-forward: x [T, hidden] bf16 and the router's
+    fp32 logits [T, E] -> [T, hidden] in x's dtype.
+
+    w_gate, w_up, w_down: sequences of E weights ([inter, hidden] twice,
+    [hidden, inter]), or a prebuilt MoeTable as w_gate alone. hidden and
+    inter must be multiples of 128; E <= 64, top_k <= 8, T * top_k <= 2048.
+    down_splits: split-K of the down projection; None picks it from the
+    shapes and the CU count (never from the routing).
+
+    GPU -> moe.hip: route, gate/up + SwiGLU, down, combine: four launches,
+    nothing read on the host, no atomics, so the call is deterministic and
+    hipGraph-capturable. CPU -> moe_ffn_ref. Inference-only."""
+    table = w_gate if isinstance(w_gate, MoeTable) else \
+        MoeTable(w_gate, w_up, w_down)
+    _moe_no_grad(x, logits, *[w for ws in table.weights for w in ws])
+    T, hidden = x.shape
+    if hidden != table.hidden or logits.shape != (
+            T, len(table.weights[0])):
+        raise ValueError("moe_ffn: x must be [T, %d] and logits [T, %d]"
+                         % (table.hidden, len(table.weights[0])))
+    _moe_check_route(T, logits.size(1), top_k)
+    if not x.is_cuda:
+        return moe_ffn_ref(x, logits, *table.weights, top_k).to(x.dtype)
+    if down_splits is not None and not \
+            1 <= down_splits <= min(table.inter // 128, 64):
+        raise ValueError("down_splits must be in [1, min(inter / 128, 64)]")
+    return hip_ext().moe_ffn(x.contiguous(), logits.float().contiguous(),
+                             table.tab, top_k, table.inter,
+                             down_splits or 0)
+
+
 # ================================ adam =====================================
 def adamw_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.95, eps=1e-8,
                weight_decay=0.1, master=None, grad_scale=1.0):
