@@ -17,7 +17,14 @@ table lookup. One JSON line per run:
 device-event time per call of both kernels (best of 3 alternating runs of
 `iters` calls, with the three runs listed), paged/contiguous, GB/s over
 the cache stream (K and V rows of the Hkv heads, once) and the worst
-per-row relative difference between the two outputs. Needs a GPU: a CPU
+per-row relative difference between the two outputs.
+
+The FP8 column is K.attn_decode_paged_fp8 (ops/csrc/decode_fp8.hip) on the
+same rows quantised with K.kv_quant_ref into the same pages, alternating
+with the other two in every round: ms per call, GB/s over the bytes ITS
+format stores for the Hkv heads (128 E4M3 bytes + one fp32 scale per row),
+and the worst per-row relative difference to the contiguous bf16 output,
+which is the accuracy cost of the format on these rows. Needs a GPU: a CPU
 timing says nothing about the kernel.
 """
 
@@ -77,6 +84,7 @@ def main():
         vc = torch.randn(B, HKV, L, D, device=dev, dtype=torch.bfloat16)
         lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
         stream_bytes = 2 * B * HKV * L * D * 2
+        fp8_bytes = 2 * B * HKV * L * (D + 4)
 
         def contiguous():
             return K.attn_decode_varlen(q, kc, vc, lengths, scale,
@@ -105,19 +113,30 @@ def main():
             kp[idx] = src_k.reshape(n, HKV, PAGE, D)
             vp[idx] = src_v.reshape(n, HKV, PAGE, D)
 
+            # the same pages in the FP8 format (quantised per row)
+            kp8, ks8 = K.kv_quant_ref(kp)
+            vp8, vs8 = K.kv_quant_ref(vp)
+
             def paged():
                 return K.attn_decode_paged(q, kp, vp, table, lengths,
                                            scale, L)
 
+            def paged_fp8():
+                return K.attn_decode_paged_fp8(q, kp8, vp8, ks8, vs8, table,
+                                               lengths, scale, L)
+
             o, ref = paged().float(), contiguous().float()
             row_err = ((o - ref).norm(dim=-1)
                        / ref.norm(dim=-1)).max().item()
-            # alternate the two kernels so drift hits both alike
-            t_p, t_c = [], []
+            fp8_err = ((paged_fp8().float() - ref).norm(dim=-1)
+                       / ref.norm(dim=-1)).max().item()
+            # alternate the kernels so drift hits all alike
+            t_p, t_c, t_8 = [], [], []
             for _ in range(3):
                 t_p.append(_time_ms(paged, args.warmup, args.iters))
+                t_8.append(_time_ms(paged_fp8, args.warmup, args.iters))
                 t_c.append(_time_ms(contiguous, args.warmup, args.iters))
-            p_ms, c_ms = min(t_p), min(t_c)
+            p_ms, c_ms, f_ms = min(t_p), min(t_c), min(t_8)
             print(json.dumps({
                 "metric": "attn_decode_paged ms/call", "shape": name,
                 "pages": order, "value": round(p_ms, 4), "unit": "ms",
@@ -129,9 +148,14 @@ def main():
                 "paged_GBps": round(stream_bytes / p_ms / 1e6, 1),
                 "contiguous_GBps": round(stream_bytes / c_ms / 1e6, 1),
                 "worst_row_rel_diff": float("%.3e" % row_err),
+                "fp8_ms": round(f_ms, 4),
+                "fp8_ms_runs": [round(t, 4) for t in t_8],
+                "fp8_GBps": round(fp8_bytes / f_ms / 1e6, 1),
+                "fp8_faster_in_every_run": max(t_8) < min(t_p),
+                "fp8_worst_row_rel_diff": float("%.3e" % fp8_err),
                 "config": {"B": B, "H": H, "Hkv": HKV, "L": L},
             }), flush=True)
-            del kp, vp
+            del kp, vp, kp8, vp8, ks8, vs8
         del q, kc, vc
 
 

@@ -3,11 +3,13 @@
 varlen flash-decode kernel), hipGraph replay vs eager decode.
 
     python benchmarks/bench_serving.py [--model llama3-8b] [--slots 8]
-        [--requests 24] [--prompt 256] [--new 64] [--pages N]
+        [--requests 24] [--prompt 256] [--new 64] [--pages N [--kv-fp8]]
         [--temperature T] [--top-k K] [--top-p P] [--seed S]
 
 --pages N serves the same request stream from a paged KV cache of N
-64-row pages (ContinuousBatcher(num_pages=N)) instead of dense slots.
+64-row pages (ContinuousBatcher(num_pages=N)) instead of dense slots;
+--kv-fp8 stores that pool as E4M3 with one fp32 scale per row
+(kv_dtype=torch.float8_e4m3fn, ops/csrc/decode_fp8.hip).
 --temperature > 0 samples every request (with the optional --top-k /
 --top-p cuts; request i is seeded --seed + i); the default decodes
 greedily.
@@ -25,13 +27,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(
 
 
 def run_one(model, graph, args, device):
+    import torch
+
     from metaflow_amd.serving import ContinuousBatcher
 
     batcher = ContinuousBatcher(model, max_batch=args.slots,
                                 max_len=args.prompt + args.new + 8,
                                 graph=graph,
                                 prefill_chunk=args.prefill_chunk,
-                                num_pages=args.pages)
+                                num_pages=args.pages,
+                                kv_dtype=(torch.float8_e4m3fn if args.kv_fp8
+                                          else None))
     random.seed(0)
     reqs = [batcher.submit(
         [random.randrange(2, 1000) for _ in
@@ -40,8 +46,6 @@ def run_one(model, graph, args, device):
         top_p=args.top_p,
         seed=None if args.seed is None else args.seed + i)
         for i in range(args.requests)]
-    import torch
-
     torch.cuda.synchronize()
     t0 = time.time()
     batcher.run()
@@ -64,6 +68,9 @@ def main():
     p.add_argument("--pages", type=int, default=None,
                    help="serve from a paged KV cache with this many "
                         "64-row pages (default: dense slots)")
+    p.add_argument("--kv-fp8", action="store_true",
+                   help="with --pages: keep the page pool in FP8 (E4M3 "
+                        "bytes + one fp32 scale per cached row)")
     p.add_argument("--temperature", type=float, default=0.0,
                    help="> 0 samples every request (default: greedy)")
     p.add_argument("--top-k", type=int, default=0)
@@ -94,7 +101,7 @@ def main():
                        "requests": args.requests,
                        "prompt_max": args.prompt, "new": args.new,
                        "prefill_chunk": args.prefill_chunk,
-                       "pages": args.pages,
+                       "pages": args.pages, "kv_fp8": args.kv_fp8,
                        "temperature": args.temperature,
                        "top_k": args.top_k, "top_p": args.top_p,
                        "seed": args.seed},

@@ -133,17 +133,30 @@ class PagedKVCache(object):
     The free list is LIFO. Reservations only count pages (admission
     control); pages are handed out by ``ensure``. Freed pages are not
     cleared: rows past a sequence's length are never read.
+
+    ``dtype=torch.float8_e4m3fn`` selects the FP8 pool
+    (ops/csrc/decode_fp8.hip): k_pages/v_pages are uint8 (E4M3 storage)
+    and k_scales/v_scales hold one fp32 scale per cached row and kv head,
+    [num_pages, Hkv, 64] per layer: 132 bytes per row and kv head where
+    bf16 takes 256. ``fp8`` tells the views which kernels to call.
     """
 
     PAGE = K.PAGE_ROWS
 
     def __init__(self, cfg, num_pages, max_batch, max_len, device,
                  dtype=torch.bfloat16):
+        self.fp8 = dtype == torch.float8_e4m3fn
         self.k_pages = [torch.zeros(num_pages, cfg.num_kv_heads, self.PAGE,
                                     cfg.head_dim, device=device,
-                                    dtype=dtype)
+                                    dtype=torch.uint8 if self.fp8 else dtype)
                         for _ in range(cfg.num_layers)]
         self.v_pages = [torch.zeros_like(k) for k in self.k_pages]
+        if self.fp8:
+            self.k_scales = [torch.zeros(num_pages, cfg.num_kv_heads,
+                                         self.PAGE, device=device,
+                                         dtype=torch.float32)
+                             for _ in range(cfg.num_layers)]
+            self.v_scales = [torch.zeros_like(t) for t in self.k_scales]
         self.num_pages = num_pages
         self.max_batch = max_batch
         self.max_len = max_len
@@ -253,9 +266,16 @@ class _PagedDecodeView(object):
 
     def attend(self, layer_idx, q, k, v, S, scale):
         """One kv_page_write of every slot's new row, one paged
-        flash-decode."""
+        flash-decode; on an FP8 pool their FP8 forms."""
         pc = self.paged
         kp, vp = pc.k_pages[layer_idx], pc.v_pages[layer_idx]
+        if pc.fp8:
+            ks, vs = pc.k_scales[layer_idx], pc.v_scales[layer_idx]
+            K.kv_page_write_fp8(k, v, kp, vp, ks, vs, pc.block_table,
+                                self.pos_t)
+            return K.attn_decode_paged_fp8(q.contiguous(), kp, vp, ks, vs,
+                                           pc.block_table, self.lengths,
+                                           scale, self.max_len)
         K.kv_page_write(k, v, kp, vp, pc.block_table, self.pos_t)
         return K.attn_decode_paged(q.contiguous(), kp, vp, pc.block_table,
                                    self.lengths, scale, self.max_len)
@@ -275,11 +295,29 @@ class PagedSlotView(object):
         chunk (pos 0) is the flash prefill on the fresh tensors; a
         one-token step is the paged decode kernel; a later chunk is the
         paged append kernel, which reads the slot's pages in place
-        through the block table (append.hip, paged instantiation)."""
+        through the block table (append.hip, paged instantiation).
+        On an FP8 pool the write and the one-token step are the FP8
+        kernels; a later chunk gathers and dequantises the slot's rows
+        (K.kv_page_gather_fp8) and runs the dense append kernel on them:
+        there is no FP8 instantiation of the paged append kernel yet."""
         pc, slot, pos = self.paged, self.slot, self.pos
         assert q.size(0) == 1, "a paged slot view holds one sequence"
         kp, vp = pc.k_pages[layer_idx], pc.v_pages[layer_idx]
         table_row = pc.block_table[slot:slot + 1]
+        if pc.fp8:
+            ks, vs = pc.k_scales[layer_idx], pc.v_scales[layer_idx]
+            K.kv_page_write_fp8(k, v, kp, vp, ks, vs, table_row, [pos])
+            if pos == 0:
+                return K.attention(q, k, v)
+            if S == 1:
+                return K.attn_decode_paged_fp8(q.contiguous(), kp, vp, ks,
+                                               vs, table_row, [pos + 1],
+                                               scale, pc.max_len)
+            n = pos + S
+            return K.attn_append(
+                q.contiguous(),
+                K.kv_page_gather_fp8(kp, ks, table_row[0], n),
+                K.kv_page_gather_fp8(vp, vs, table_row[0], n), pos, scale)
         K.kv_page_write(k, v, kp, vp, table_row, [pos])
         if pos == 0:
             return K.attention(q, k, v)

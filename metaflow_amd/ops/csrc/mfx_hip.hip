@@ -14,6 +14,7 @@
 #include "paged.hip"
 #include "decode.hip"
 #include "append.hip"
+#include "decode_fp8.hip"
 #include "sampling.hip"
 #include "moe.hip"
 #include "debug_kernels.hip"
@@ -697,6 +698,95 @@ void kv_page_write(torch::Tensor k, torch::Tensor v, torch::Tensor kp,
   HIP_CHECK_KERNEL();
 }
 
+// ------------------------------------------------- FP8 paged KV cache
+// E4M3 pools [num_pages, Hkv, 64, 128] uint8 with one fp32 scale per row
+// and kv head, [num_pages, Hkv, 64] (decode_fp8.hip). Neither call reads
+// lengths / pos on the host: both are hipGraph-capturable.
+void check_fp8_pool(const torch::Tensor& kp, const torch::Tensor& vp,
+                    const torch::Tensor& ks, const torch::Tensor& vs) {
+  for (const torch::Tensor* t : {&kp, &vp})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kUInt8 &&
+                t->is_contiguous() && t->dim() == 4 &&
+                t->size(2) == PG_ROWS && t->size(3) == PG_D,
+                "FP8 page pool must be contiguous uint8 "
+                "[num_pages, Hkv, 64, 128] on GPU");
+  TORCH_CHECK(vp.sizes() == kp.sizes(),
+              "k_pages and v_pages must have the same shape");
+  for (const torch::Tensor* t : {&ks, &vs})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
+                t->is_contiguous() && t->dim() == 3 &&
+                t->size(0) == kp.size(0) && t->size(1) == kp.size(1) &&
+                t->size(2) == PG_ROWS,
+                "FP8 page scales must be contiguous fp32 "
+                "[num_pages, Hkv, 64] on GPU");
+}
+
+void kv_page_write_fp8(torch::Tensor k, torch::Tensor v, torch::Tensor kp,
+                       torch::Tensor vp, torch::Tensor ks, torch::Tensor vs,
+                       torch::Tensor table, torch::Tensor pos) {
+  check_new_rows(k, "k");
+  check_new_rows(v, "v");
+  check_fp8_pool(kp, vp, ks, vs);
+  TORCH_CHECK(v.sizes() == k.sizes(), "k and v must have the same shape");
+  const int B = k.size(0), Hkv = k.size(1), S = k.size(2);
+  TORCH_CHECK(kp.size(1) == Hkv, "k and the pool disagree on Hkv");
+  check_block_table(table, B);
+  check_int32_vec(pos, B, "pos");
+  const long long vecs = (long long)B * Hkv * S * (PG_D / 8);
+  if (vecs == 0) return;
+  kv_page_write_fp8_kernel<<<grid_for(vecs), kBlock, 0, cur_stream()>>>(
+      bf(k), bf(v), kp.data_ptr<uint8_t>(), vp.data_ptr<uint8_t>(),
+      ks.data_ptr<float>(), vs.data_ptr<float>(), table.data_ptr<int>(),
+      pos.data_ptr<int>(), B, Hkv, S, (int)kp.size(0), (int)table.size(1),
+      k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
+      v.stride(2));
+  HIP_CHECK_KERNEL();
+}
+
+// One block per (split, kv head, sequence) serves the G = H / Hkv heads
+// of the kv head; the split count is the bf16 paged decode's (from
+// capacities only), and the partials go through its merge kernel.
+torch::Tensor attn_decode_paged_fp8(torch::Tensor q, torch::Tensor kp,
+                                    torch::Tensor vp, torch::Tensor ks,
+                                    torch::Tensor vs, torch::Tensor table,
+                                    torch::Tensor lengths, long max_len,
+                                    double scale) {
+  check_bf16(q, "q");
+  check_fp8_pool(kp, vp, ks, vs);
+  TORCH_CHECK(q.dim() == 4 && q.size(2) == 1 && q.size(3) == PG_D,
+              "FP8 paged decode expects q [B,H,1,128]");
+  const int B = q.size(0), H = q.size(1);
+  const int num_pages = kp.size(0), Hkv = kp.size(1);
+  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  TORCH_CHECK(H / Hkv <= KV8_MAX_G,
+              "FP8 paged decode serves at most 32 heads per kv head");
+  check_block_table(table, B);
+  const int table_stride = table.size(1);
+  TORCH_CHECK(max_len >= 1 && max_len <= (long)table_stride * PG_ROWS,
+              "max_len must be in [1, 64 * pages_per_seq]");
+  check_int32_vec(lengths, B, "lengths");
+  const int splits = (int)std::min<long>(
+      decode_splits(B, H, max_len), (max_len + PG_ROWS - 1) / PG_ROWS);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto o_part = torch::empty({splits, B, H, 128}, f32);
+  auto ml_part = torch::empty({splits, B, H, 2}, f32);
+  auto o = torch::empty_like(q);
+  attn_decode_paged_fp8_partial_kernel<<<dim3(splits, Hkv, B),
+                                         KV8_WAVES * WAVE, 0,
+                                         cur_stream()>>>(
+      bf(q), kp.data_ptr<uint8_t>(), vp.data_ptr<uint8_t>(),
+      ks.data_ptr<float>(), vs.data_ptr<float>(), table.data_ptr<int>(),
+      lengths.data_ptr<int>(), o_part.data_ptr<float>(),
+      ml_part.data_ptr<float>(), B, H, Hkv, num_pages, table_stride, splits,
+      (float)scale);
+  HIP_CHECK_KERNEL();
+  attn_decode_merge_kernel<<<B * H, 64, 0, cur_stream()>>>(
+      o_part.data_ptr<float>(), ml_part.data_ptr<float>(), bfm(o), B, H,
+      splits);
+  HIP_CHECK_KERNEL();
+  return o;
+}
+
 // ------------------------------------------------------------ sampling
 // [B, V] logits (bf16 or fp32, dense last dim, any row stride) -> int64 [B]
 // token ids, every parameter per row and on the device: no host read, one
@@ -940,6 +1030,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_page_write", &kv_page_write,
         "scatter new K/V rows [B,Hkv,S,128] into the page pool at "
         "pos[b].. through the block table (pos < 0 skips the sequence)");
+  m.def("kv_page_write_fp8", &kv_page_write_fp8,
+        "quantise new K/V rows to E4M3 with one fp32 scale per row and "
+        "scatter them into the FP8 page pool through the block table");
+  m.def("attn_decode_paged_fp8", &attn_decode_paged_fp8,
+        "GQA-packed MFMA flash-decode over an FP8 (E4M3 + row scales) "
+        "paged KV cache");
   m.def("sample_tokens", &sample_tokens,
         "fused sampler: logits [B,V] (bf16/fp32) + per-row temperature, "
         "top_k, top_p, u -> int64 [B] token ids (temperature <= 0 = "

@@ -738,6 +738,118 @@ def kv_page_write(k, v, k_pages, v_pages, block_table, pos):
             v_pages[page, :, r] = v[b, :, s]
 
 
+# ========================== FP8 paged KV cache =============================
+# Pools [num_pages, Hkv, 64, 128] uint8 (float8_e4m3fn storage, the
+# convention of ops/fp8.py) with one fp32 scale per cached row and kv head,
+# [num_pages, Hkv, 64]: a row is quantised once, when it is written
+# (ops/csrc/decode_fp8.hip).
+E4M3_MAX = 448.0
+
+
+def kv_quant_ref(x):
+    """Quantise rows x[..., 128] to the FP8 cache format, in fp32:
+    amax = max|x|, scale = amax / 448, byte = RNE-E4M3 of
+    clamp(x * (448 / amax), -448, 448); a zero row gives zero bytes and
+    scale 0. Returns (bytes uint8 [..., 128], scale fp32 [...]). Torch
+    composition for any device: the definition of the format."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    scale = amax / E4M3_MAX
+    inv = torch.where(amax > 0, E4M3_MAX / amax, torch.zeros_like(amax))
+    y = (xf * inv.unsqueeze(-1)).clamp(-E4M3_MAX, E4M3_MAX)
+    return y.to(torch.float8_e4m3fn).view(torch.uint8), scale
+
+
+def kv_dequant_ref(qbytes, scale):
+    """fp32 values of FP8 cache rows: e4m3(byte) * scale."""
+    return qbytes.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)
+
+
+def _kv_gather_fp8_f32(pages, scales, table_row, n):
+    """The first ``n`` rows of one sequence of an FP8 pool, dequantised to
+    fp32 [1, Hkv, n, 128]."""
+    npg = (n + PAGE_ROWS - 1) // PAGE_ROWS
+    idx = table_row[:npg].to(device=pages.device, dtype=torch.long)
+    g = kv_dequant_ref(pages[idx], scales[idx])     # [npg, Hkv, 64, 128]
+    g = g.permute(1, 0, 2, 3).reshape(1, pages.size(1), npg * PAGE_ROWS,
+                                      pages.size(3))
+    return g[:, :, :n].contiguous()
+
+
+def kv_page_gather_fp8(pages, scales, table_row, n):
+    """The first ``n`` rows of one sequence of an FP8 pool, dequantised
+    and rounded to bf16, as a contiguous [1, Hkv, n, 128] tensor. Plain
+    torch on both devices, like kv_page_gather: tests, and the stop-gap
+    for prefill chunks at pos > 0 (PagedSlotView)."""
+    return _kv_gather_fp8_f32(pages, scales, table_row, n).to(torch.bfloat16)
+
+
+def kv_page_write_fp8(k, v, k_pages, v_pages, k_scales, v_scales,
+                      block_table, pos):
+    """kv_page_write into an FP8 pool: the new rows k, v [B, Hkv, S, 128]
+    (bf16) are quantised per row (kv_quant_ref) and written, bytes and
+    scales, at rows pos[b] .. pos[b]+S-1 of sequence b through the block
+    table. Same contract: pos is never read on the host, pos[b] < 0 skips
+    the sequence.
+    GPU -> decode_fp8.hip, K and V in one launch; CPU -> index
+    assignment."""
+    if k.is_cuda:
+        if not torch.is_tensor(pos):
+            pos = torch.tensor(pos, dtype=torch.int32, device=k.device)
+        pos = pos.to(device=k.device, dtype=torch.int32).contiguous()
+        hip_ext().kv_page_write_fp8(_rows16(k), _rows16(v), k_pages,
+                                    v_pages, k_scales, v_scales,
+                                    block_table, pos)
+        return
+    kq, ks = kv_quant_ref(k)
+    vq, vs = kv_quant_ref(v)
+    S = k.size(2)
+    for b, p in enumerate(_pos_list(pos, k.size(0))):
+        if p < 0:
+            continue
+        for s in range(S):
+            page = int(block_table[b, (p + s) // PAGE_ROWS])
+            assert page >= 0, "write to a row that has no page"
+            r = (p + s) % PAGE_ROWS
+            k_pages[page, :, r] = kq[b, :, s]
+            v_pages[page, :, r] = vq[b, :, s]
+            k_scales[page, :, r] = ks[b, :, s]
+            v_scales[page, :, r] = vs[b, :, s]
+
+
+def attn_decode_paged_fp8(q, k_pages, v_pages, k_scales, v_scales,
+                          block_table, lengths, scale, max_len):
+    """attn_decode_paged over an FP8 pool: one query row per (b, h)
+    against the first lengths[b] rows of sequence b (length 0 = inactive
+    slot, output row zero). All H / Hkv <= 32 heads of a kv head are served
+    from one pass over its pages.
+
+    q: [B, H, 1, 128] bf16; k_pages/v_pages: [num_pages, Hkv, 64, 128]
+    uint8; k_scales/v_scales: [num_pages, Hkv, 64] fp32; block_table,
+    lengths, ``max_len``: as in attn_decode_paged (lengths is never read
+    on the host: always hipGraph-capturable).
+    GPU -> decode_fp8.hip; CPU -> gather through the table, dequantise,
+    fp32 reference.
+    """
+    if q.is_cuda:
+        lengths = _lengths_tensor(lengths, q.device)
+        return hip_ext().attn_decode_paged_fp8(
+            q.contiguous(), k_pages, v_pages, k_scales, v_scales,
+            block_table, lengths, max_len, scale)
+    outs = []
+    for b in range(q.size(0)):
+        n = int(lengths[b])
+        if n == 0:
+            outs.append(torch.zeros_like(q[b:b + 1]))
+            continue
+        outs.append(attention_ref(
+            q[b:b + 1],
+            _kv_gather_fp8_f32(k_pages, k_scales, block_table[b], n),
+            _kv_gather_fp8_f32(v_pages, v_scales, block_table[b], n),
+            scale, causal=False))
+    return torch.cat(outs, 0)
+
+
 # ============================== sampling ===================================
 _FLT_BIG = 3.0e38  # bound on 1/T: a denormal T must not make 0 * inf
 

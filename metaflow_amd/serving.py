@@ -92,7 +92,7 @@ _GREEDY = (0.0, 0, 1.0)
 
 class ContinuousBatcher(object):
     def __init__(self, model, max_batch=8, max_len=2048, graph="auto",
-                 prefill_chunk=None, num_pages=None):
+                 prefill_chunk=None, num_pages=None, kv_dtype=None):
         """graph: capture the whole decode step in a hipGraph and replay
         it per token (decode is LAUNCH-bound — ~200 small kernels per
         step; replay collapses them to one submit). "auto" captures on
@@ -118,7 +118,13 @@ class ContinuousBatcher(object):
         ceil((len(prompt) + max_new) / 64) pages for the head request —
         it waits (and everything behind it) until they fit, so no
         request runs out of pages mid-decode and nothing is preempted.
-        Physical pages are allocated lazily as rows are written."""
+        Physical pages are allocated lazily as rows are written.
+
+        kv_dtype: None keeps the cache in the model's dtype.
+        ``torch.float8_e4m3fn`` (paged cache only) stores the pool as
+        E4M3 bytes with one fp32 scale per cached row and kv head
+        (ops/csrc/decode_fp8.hip): 132 bytes per row and kv head
+        where bf16 takes 256, so the same memory holds 1.94x the rows."""
         import torch
 
         from .models.kv_cache import KVCache, PagedKVCache
@@ -129,10 +135,13 @@ class ContinuousBatcher(object):
         device = next(model.parameters()).device
         self.device = device
         self.paged = num_pages is not None
+        if kv_dtype is not None and not self.paged:
+            raise ValueError("kv_dtype needs the paged cache: pass num_pages")
         if self.paged:
-            self.cache = PagedKVCache(model.cfg, num_pages, max_batch,
-                                      max_len, device,
-                                      dtype=model.embed.weight.dtype)
+            self.cache = PagedKVCache(
+                model.cfg, num_pages, max_batch, max_len, device,
+                dtype=(model.embed.weight.dtype if kv_dtype is None
+                       else kv_dtype))
         else:
             self.cache = KVCache(model.cfg, max_batch, max_len, device,
                                  dtype=model.embed.weight.dtype)
