@@ -21,6 +21,14 @@ the same rows held in a page pool: pages in order, pages randomly permuted, and 
 paged engine took before that kernel existed (K.kv_page_gather of K and
 of V, then K.attn_append on the copies), each next to the dense kernel.
 All of them alternate within each of the three runs.
+
+A third JSON line per shape covers the FP8 pool (K.attn_append_paged_fp8,
+ops/csrc/append_fp8.hip) on the same rows quantised to E4M3 with row
+scales: the kernel, the path the FP8 engine took before it
+(K.kv_page_gather_fp8 of K and of V, then K.attn_append) and the bf16
+paged kernel alternate within each run, in both page orders. GB/s counts
+the bytes the format stores, 132 per row and kv head for K and for V.
+--fp8-only prints only that line.
 """
 
 import argparse
@@ -56,18 +64,18 @@ def _time_ms(fn, warmup, iters):
     return start.elapsed_time(stop) / iters
 
 
-def _pool(torch, cache, table, num_pages):
-    """Page pool [num_pages, Hkv, 64, 128] holding the rows of
-    cache [1, Hkv, L, 128] at the pages table [pps] names (zeros
+def _pool(torch, cache, table, num_pages, d=D):
+    """Page pool [num_pages, Hkv, 64, d] holding the rows of
+    cache [1, Hkv, L, d] at the pages table [pps] names (zeros
     elsewhere)."""
     hkv, L = cache.size(1), cache.size(2)
     pps = table.numel()
-    padded = torch.zeros(hkv, pps * PAGE, D, device=cache.device,
+    padded = torch.zeros(hkv, pps * PAGE, d, device=cache.device,
                          dtype=cache.dtype)
     padded[:, :L] = cache[0]
-    pool = torch.zeros(num_pages, hkv, PAGE, D, device=cache.device,
+    pool = torch.zeros(num_pages, hkv, PAGE, d, device=cache.device,
                        dtype=cache.dtype)
-    pool[table.long()] = padded.view(hkv, pps, PAGE, D).permute(1, 0, 2, 3)
+    pool[table.long()] = padded.view(hkv, pps, PAGE, d).permute(1, 0, 2, 3)
     return pool
 
 
@@ -142,10 +150,89 @@ def _paged_row(K, torch, name, Sq, pos, q, kc, vc, pos_t, scale, dense,
     return res
 
 
+def _fp8_row(K, torch, name, Sq, pos, q, kc, vc, pos_t, scale, args):
+    """The FP8 paged kernel, the gather + dense path on the same FP8
+    pools, and the bf16 paged kernel on the unquantised rows."""
+    L = pos + Sq
+    pps = -(-L // PAGE)
+    num_pages = pps + 8
+    gen = torch.Generator().manual_seed(1)
+    tables = {
+        "in_order": torch.arange(pps, dtype=torch.int32),
+        "permuted": torch.randperm(num_pages, generator=gen)[:pps].to(
+            torch.int32),
+    }
+    (kq, ksc), (vq, vsc) = K.kv_quant_ref(kc), K.kv_quant_ref(vc)
+    fns, checks = {}, {}
+    for order, tbl in tables.items():
+        tbl = tbl.to(q.device)
+        tb = tbl.view(1, pps).contiguous()
+        pool = [_pool(torch, kq, tbl, num_pages),
+                _pool(torch, vq, tbl, num_pages),
+                _pool(torch, ksc.unsqueeze(-1), tbl, num_pages, 1)[..., 0]
+                .contiguous(),
+                _pool(torch, vsc.unsqueeze(-1), tbl, num_pages, 1)[..., 0]
+                .contiguous()]
+        kp16 = _pool(torch, kc, tbl, num_pages)
+        vp16 = _pool(torch, vc, tbl, num_pages)
+
+        def fp8(pool=pool, tb=tb):
+            return K.attn_append_paged_fp8(q, *pool, tb, pos_t, scale,
+                                           max_len=L)
+
+        def gather(pool=pool, tb=tb):
+            kg = K.kv_page_gather_fp8(pool[0], pool[2], tb[0], L)
+            vg = K.kv_page_gather_fp8(pool[1], pool[3], tb[0], L)
+            return K.attn_append(q, kg, vg, pos_t, scale, max_len=L)
+
+        def bf16(kp=kp16, vp=vp16, tb=tb):
+            return K.attn_append_paged(q, kp, vp, tb, pos_t, scale,
+                                       max_len=L)
+
+        fns["fp8_" + order] = fp8
+        fns["gather_" + order] = gather
+        fns["bf16_" + order] = bf16
+        o, og = fp8().float(), gather().float()
+        d = (o - og).norm(dim=-1) / og.norm(dim=-1)
+        checks[order] = {"worst_row_rel_diff_to_gather_path":
+                         float("%.3e" % d.max().item())}
+    runs = {k: [] for k in fns}
+    for _ in range(3):
+        for k, fn in fns.items():
+            runs[k].append(_time_ms(fn, args.warmup, args.iters))
+    best = {k: min(v) for k, v in runs.items()}
+    flops = 4.0 * B * H * Sq * D * (pos + (Sq + 1) / 2.0)
+    stored = 2 * B * HKV * L * (D + 4)
+    return {
+        "metric": "attn_append_paged_fp8 ms/call", "shape": name,
+        "value": round(best["fp8_in_order"], 4), "unit": "ms",
+        "higher_is_better": False,
+        "best_ms": {k: round(v, 4) for k, v in best.items()},
+        "ms_runs": {k: [round(t, 4) for t in v] for k, v in runs.items()},
+        "every_fp8_run_below_every_gather_run": {
+            o: max(runs["fp8_" + o]) < min(runs["gather_" + o])
+            for o in tables},
+        "gather_path_over_fp8": {
+            o: round(best["gather_" + o] / best["fp8_" + o], 2)
+            for o in tables},
+        "fp8_over_bf16_paged": {
+            o: round(best["fp8_" + o] / best["bf16_" + o], 3)
+            for o in tables},
+        "tflops": {o: round(flops / (best["fp8_" + o] * 1e9), 2)
+                   for o in tables},
+        "stored_GBps": {o: round(stored / best["fp8_" + o] / 1e6, 1)
+                        for o in tables},
+        "vs_gather_path": checks,
+        "config": {"B": B, "H": H, "Hkv": HKV, "Sq": Sq, "pos": pos,
+                   "pages": pps, "pool_pages": num_pages},
+    }
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--fp8-only", action="store_true")
     args = p.parse_args()
 
     import torch
@@ -171,6 +258,10 @@ def main():
         def eager():
             return K.attn_append_ref(q, kc, vc, pos, scale)
 
+        if args.fp8_only:
+            print(json.dumps(_fp8_row(K, torch, name, Sq, pos, q, kc, vc,
+                                      pos_t, scale, args)), flush=True)
+            continue
         o, ref = kern().float(), eager().float()
         row_err = ((o - ref).norm(dim=-1) / ref.norm(dim=-1)).max().item()
         # alternate the two paths so drift hits both alike
@@ -205,6 +296,8 @@ def main():
         print(json.dumps(res), flush=True)
         print(json.dumps(_paged_row(K, torch, name, Sq, pos, q, kc, vc,
                                     pos_t, scale, kern, args)), flush=True)
+        print(json.dumps(_fp8_row(K, torch, name, Sq, pos, q, kc, vc, pos_t,
+                                  scale, args)), flush=True)
         del q, kc, vc
 
 

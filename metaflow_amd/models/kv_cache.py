@@ -296,10 +296,9 @@ class PagedSlotView(object):
         one-token step is the paged decode kernel; a later chunk is the
         paged append kernel, which reads the slot's pages in place
         through the block table (append.hip, paged instantiation).
-        On an FP8 pool the write and the one-token step are the FP8
-        kernels; a later chunk gathers and dequantises the slot's rows
-        (K.kv_page_gather_fp8) and runs the dense append kernel on them:
-        there is no FP8 instantiation of the paged append kernel yet."""
+        On an FP8 pool the write, the one-token step and the later chunk
+        are the FP8 kernels (decode_fp8.hip, append_fp8.hip): every shape
+        reads the E4M3 pages in place."""
         pc, slot, pos = self.paged, self.slot, self.pos
         assert q.size(0) == 1, "a paged slot view holds one sequence"
         kp, vp = pc.k_pages[layer_idx], pc.v_pages[layer_idx]
@@ -313,11 +312,9 @@ class PagedSlotView(object):
                 return K.attn_decode_paged_fp8(q.contiguous(), kp, vp, ks,
                                                vs, table_row, [pos + 1],
                                                scale, pc.max_len)
-            n = pos + S
-            return K.attn_append(
-                q.contiguous(),
-                K.kv_page_gather_fp8(kp, ks, table_row[0], n),
-                K.kv_page_gather_fp8(vp, vs, table_row[0], n), pos, scale)
+            return K.attn_append_paged_fp8(q.contiguous(), kp, vp, ks, vs,
+                                           table_row, [pos], scale,
+                                           pc.max_len)
         K.kv_page_write(k, v, kp, vp, table_row, [pos])
         if pos == 0:
             return K.attention(q, k, v)

@@ -15,6 +15,7 @@
 #include "decode.hip"
 #include "append.hip"
 #include "decode_fp8.hip"
+#include "append_fp8.hip"
 #include "sampling.hip"
 #include "moe.hip"
 #include "debug_kernels.hip"
@@ -526,12 +527,14 @@ AppendPlan append_plan(int B, int H, int Sq, long max_len) {
 
 // Partials (with splits > 1), the dense (table == nullptr: kc/vc
 // [B,Hkv,Lmax,128]) or the paged (kc/vc the pool) instantiation of
-// append.hip at the plan's block size, and the merge.
+// append.hip at the plan's block size, and the merge. With ksc / vsc the
+// pool is the E4M3 one and the kernel that of append_fp8.hip.
 torch::Tensor append_launch(torch::Tensor& q, const torch::Tensor& kc,
                             const torch::Tensor& vc, const int* table,
                             const torch::Tensor& pos, int Hkv, int Lmax,
                             int num_pages, int table_stride, long max_len,
-                            double scale) {
+                            double scale, const float* ksc = nullptr,
+                            const float* vsc = nullptr) {
   const int B = q.size(0), H = q.size(1), Sq = q.size(2);
   const AppendPlan plan = append_plan(B, H, Sq, max_len);
   const int splits = plan.splits;
@@ -549,6 +552,13 @@ torch::Tensor append_launch(torch::Tensor& q, const torch::Tensor& kc,
   dim3 grid(plan.q_tiles * splits, H, B);
   auto launch = [&](auto nw) {
     constexpr int NW = decltype(nw)::value;
+    if (ksc) {
+      attn_append_paged_fp8_kernel<NW><<<grid, NW * WAVE, 0, cur_stream()>>>(
+          bf(q), kc.data_ptr<uint8_t>(), vc.data_ptr<uint8_t>(), ksc, vsc,
+          table, pos.data_ptr<int>(), bfm(o), o_part_p, ml_part_p, B, H,
+          Hkv, Sq, num_pages, table_stride, splits, (float)scale);
+      return;
+    }
     if (table)
       attn_append_paged_kernel<NW><<<grid, NW * WAVE, 0, cur_stream()>>>(
           bf(q), bf(kc), bf(vc), table, pos.data_ptr<int>(), bfm(o),
@@ -785,6 +795,30 @@ torch::Tensor attn_decode_paged_fp8(torch::Tensor q, torch::Tensor kp,
       splits);
   HIP_CHECK_KERNEL();
   return o;
+}
+
+// Append attention over the FP8 pool (append_fp8.hip): the contract, the
+// launch plan and the merge of attn_append_paged.
+torch::Tensor attn_append_paged_fp8(torch::Tensor q, torch::Tensor kp,
+                                    torch::Tensor vp, torch::Tensor ks,
+                                    torch::Tensor vs, torch::Tensor table,
+                                    torch::Tensor pos, long max_len,
+                                    double scale) {
+  check_bf16(q, "q");
+  check_fp8_pool(kp, vp, ks, vs);
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == PG_D && q.size(2) >= 1,
+              "FP8 paged append expects q [B,H,Sq,128]");
+  const int B = q.size(0), H = q.size(1);
+  const int num_pages = kp.size(0), Hkv = kp.size(1);
+  TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  check_block_table(table, B);
+  const int table_stride = table.size(1);
+  TORCH_CHECK(max_len >= 1 && max_len <= (long)table_stride * PG_ROWS,
+              "max_len must be in [1, 64 * pages_per_seq]");
+  check_int32_vec(pos, B, "pos");
+  return append_launch(q, kp, vp, table.data_ptr<int>(), pos, Hkv, 0,
+                       num_pages, table_stride, max_len, scale,
+                       ks.data_ptr<float>(), vs.data_ptr<float>());
 }
 
 // ------------------------------------------------------------ sampling
@@ -1036,6 +1070,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_paged_fp8", &attn_decode_paged_fp8,
         "GQA-packed MFMA flash-decode over an FP8 (E4M3 + row scales) "
         "paged KV cache");
+  m.def("attn_append_paged_fp8", &attn_append_paged_fp8,
+        "append attention over an FP8 (E4M3 + row scales) paged KV cache: "
+        "q [B,H,Sq,128], block table int32 [B,pages], pos int32 [B] "
+        "(pos < 0 = output 0)");
   m.def("sample_tokens", &sample_tokens,
         "fused sampler: logits [B,V] (bf16/fp32) + per-row temperature, "
         "top_k, top_p, u -> int64 [B] token ids (temperature <= 0 = "

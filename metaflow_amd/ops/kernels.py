@@ -779,8 +779,8 @@ def _kv_gather_fp8_f32(pages, scales, table_row, n):
 def kv_page_gather_fp8(pages, scales, table_row, n):
     """The first ``n`` rows of one sequence of an FP8 pool, dequantised
     and rounded to bf16, as a contiguous [1, Hkv, n, 128] tensor. Plain
-    torch on both devices, like kv_page_gather: tests, and the stop-gap
-    for prefill chunks at pos > 0 (PagedSlotView)."""
+    torch on both devices, like kv_page_gather: a utility for tests and
+    references, on no model path."""
     return _kv_gather_fp8_f32(pages, scales, table_row, n).to(torch.bfloat16)
 
 
@@ -848,6 +848,42 @@ def attn_decode_paged_fp8(q, k_pages, v_pages, k_scales, v_scales,
             _kv_gather_fp8_f32(v_pages, v_scales, block_table[b], n),
             scale, causal=False))
     return torch.cat(outs, 0)
+
+
+def attn_append_paged_fp8(q, k_pages, v_pages, k_scales, v_scales,
+                          block_table, pos, scale, max_len=None):
+    """attn_append_paged over an FP8 pool: Sq new query rows per sequence
+    at offset ``pos`` against the rows the sequence owns, which already
+    hold the new rows at pos .. pos+Sq-1 (written by kv_page_write_fp8).
+    Query row i of sequence b attends to rows 0 .. pos[b]+i. The shape of
+    every prefill chunk after the first on an FP8 PagedKVCache; the pool is
+    read in place, nothing is gathered or dequantised to memory.
+
+    q: [B, H, Sq, 128] bf16; k_pages/v_pages: [num_pages, Hkv, 64, 128]
+    uint8; k_scales/v_scales: [num_pages, Hkv, 64] fp32; block_table,
+    ``pos`` and ``max_len``: as in attn_append_paged (holes contribute no
+    key, pos[b] < 0 gives zero rows, and with ``pos`` a device tensor and
+    ``max_len`` given nothing is read on the host).
+    GPU -> append_fp8.hip; CPU -> gather through the table, dequantise,
+    attn_append_ref.
+    """
+    B, Sq = q.size(0), q.size(2)
+    if not q.is_cuda:
+        outs = []
+        for b, p in enumerate(_pos_list(pos, B)):
+            if p < 0:
+                outs.append(torch.zeros_like(q[b:b + 1]))
+                continue
+            outs.append(attn_append_ref(
+                q[b:b + 1],
+                _kv_gather_fp8_f32(k_pages, k_scales, block_table[b], p + Sq),
+                _kv_gather_fp8_f32(v_pages, v_scales, block_table[b], p + Sq),
+                p, scale))
+        return torch.cat(outs, 0)
+    pos_t, max_len = _pos_tensor(pos, q, max_len)
+    return hip_ext().attn_append_paged_fp8(
+        q.contiguous(), k_pages, v_pages, k_scales, v_scales, block_table,
+        pos_t, max_len, scale)
 
 
 # ============================== sampling ===================================
