@@ -4,6 +4,8 @@
     python benchmarks/bench_decode.py [--model llama3-8b] [--batch 8]
         [--prompt 512] [--new 128]
     python benchmarks/bench_decode.py --model mixtral-tiny --fused-moe
+    python benchmarks/bench_decode.py --model mixtral-tiny \
+        --fused-moe-prefill --prompt-range 1024 2047
 
 Measures prefill time and per-token decode rate separately. The decode
 attention runs the split-K flash-decode kernel (ops/csrc/decode.hip)
@@ -14,6 +16,12 @@ continuous batcher over --batch requests of --new tokens with the eager MoE
 block, with the fused block (cfg.fused_moe_decode, ops/csrc/moe.hip) run
 eagerly, and with the fused block replayed from a captured hipGraph, which
 only the fused block allows.
+
+--fused-moe-prefill (mixtral-tiny) keeps the fused decode block and graph
+replay in both contestants and switches the prefill's MoE block: eager
+(MoELayer.forward) against fused (cfg.fused_moe_prefill,
+ops/csrc/moe_prefill.hip above 32 entries per expert), over --batch prompts
+of lengths drawn once from --prompt-range.
 """
 
 import argparse
@@ -84,6 +92,59 @@ def fused_moe_serving(args, device):
     }), flush=True)
 
 
+def fused_moe_prefill_serving(args, device):
+    """Tokens/s (prompt + new) of ContinuousBatcher.run() on tiny Mixtral
+    with the eager and the fused prefill block, 3 alternating rounds after
+    a warm-up round, every run listed."""
+    import torch
+
+    from metaflow_amd.models.mixtral import (
+        MixtralConfig,
+        MixtralForCausalLM,
+    )
+    from metaflow_amd.serving import ContinuousBatcher
+
+    assert device.type == "cuda", "--fused-moe-prefill measures on a GPU"
+    lo, hi = args.prompt_range
+    cfg = MixtralConfig.tiny(seq=hi + args.new + 64)
+    cfg.fused_moe_decode = True
+    torch.manual_seed(0)
+    with torch.device(device):
+        model = MixtralForCausalLM(cfg)
+    model.eval()
+    g = torch.Generator().manual_seed(0)
+    lens = torch.randint(lo, hi + 1, (args.batch,), generator=g).tolist()
+    prompts = [torch.randint(0, cfg.vocab_size, (n,), generator=g).tolist()
+               for n in lens]
+    total = sum(lens) + args.batch * args.new
+    runs = {"eager_prefill": [], "fused_prefill": []}
+    for rnd in range(4):  # round 0 warms up
+        for name in runs:
+            cfg.fused_moe_prefill = name == "fused_prefill"
+            b = ContinuousBatcher(model, max_batch=args.batch,
+                                  max_len=hi + args.new + 64, graph=True,
+                                  prefill_chunk=args.prefill_chunk)
+            reqs = [b.submit(pr, args.new) for pr in prompts]
+            torch.cuda.synchronize()
+            t0 = time.time()
+            out = b.run()
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+            assert all(len(out[r.id]) == args.new for r in reqs)
+            if rnd:
+                runs[name].append(round(total / dt, 1))
+    cfg.fused_moe_prefill = False
+    print(json.dumps({
+        "metric": "serving tokens/sec, prompt and new tokens (fused MoE "
+                  "decode, graph replay)",
+        "unit": "tokens/s", "higher_is_better": True, "runs": runs,
+        "config": {"model": args.model, "batch": args.batch,
+                   "prompt_lens": lens, "new": args.new,
+                   "prefill_chunk": args.prefill_chunk,
+                   "device": str(device)},
+    }), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="llama3-8b",
@@ -94,9 +155,21 @@ def main():
     p.add_argument("--fused-moe", action="store_true",
                    help="mixtral-tiny: serving decode, eager MoE vs fused "
                         "MoE (eager and graph replay)")
+    p.add_argument("--fused-moe-prefill", action="store_true",
+                   help="mixtral-tiny: serving with the eager vs the fused "
+                        "MoE block at prefill")
+    p.add_argument("--prompt-range", type=int, nargs=2, default=[128, 255],
+                   metavar=("LO", "HI"),
+                   help="--fused-moe-prefill: prompt lengths")
+    p.add_argument("--prefill-chunk", type=int, default=None,
+                   help="--fused-moe-prefill: the batcher's prefill_chunk "
+                        "(the fused block serves up to 384 entries per "
+                        "expert, 768 tokens of mixtral-tiny, per call)")
     args = p.parse_args()
-    if args.fused_moe and args.model != "mixtral-tiny":
-        p.error("--fused-moe needs --model mixtral-tiny")
+    if (args.fused_moe or args.fused_moe_prefill) and \
+            args.model != "mixtral-tiny":
+        p.error("--fused-moe and --fused-moe-prefill need --model "
+                "mixtral-tiny")
 
     import torch
 
@@ -110,6 +183,8 @@ def main():
     device = torch.device("cuda", 0) if use_gpu else torch.device("cpu")
     if args.fused_moe:
         return fused_moe_serving(args, device)
+    if args.fused_moe_prefill:
+        return fused_moe_prefill_serving(args, device)
     factories = {
         "llama3-8b": (LlamaConfig.llama3_8b, LlamaForCausalLM),
         "tiny": (LlamaConfig.tiny, LlamaForCausalLM),

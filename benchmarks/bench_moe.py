@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
-"""One MoE feed-forward block at decode time: the eager block
-(MoELayer.forward: torch routing, a Python loop over the experts with a host
-read each, hipBLASLt GEMMs) against the fused one (MoELayer.decode: moe.hip).
+"""One MoE feed-forward block: the eager block (MoELayer.forward: torch
+routing, a Python loop over the experts with a host read each, hipBLASLt
+GEMMs) against the fused one on its two paths: "stream" (moe.hip, the
+decode kernels, T * top_k <= 2048) and "tiled" (moe_prefill.hip, the
+prefill kernels).
 
-    python benchmarks/bench_moe.py [--tokens 1 8 32 64] [--rounds 3]
-        [--iters 200]
+    python benchmarks/bench_moe.py [--tokens 1 8 32 64 128 256 1024 4096]
+        [--path stream tiled] [--rounds 3] [--iters 200]
 
 Mixtral 8x7B geometry by default (hidden 4096, inter 14336, E = 8, k = 2).
-Per T the two paths alternate for --rounds rounds; a run is --iters calls
-between two device events, after a warm-up of both. Every run is listed.
+Per T the contestants alternate for --rounds rounds; a run is --iters calls
+between two device events, after a warm-up of all. Every run is listed.
 The bytes are those of the gate, up and down weights of the experts the
 router actually hit for that input, each counted once; GB/s is those bytes
-over the time of one call, next to the 8 TB/s HBM peak of the MI355X. One
-JSON line per T, then a summary line.
+over the time of one call, next to the 8 TB/s HBM peak of the MI355X. The
+FLOPs are those of the routed entries, 6 * T * top_k * hidden * inter;
+TFLOP/s next to the 2.5 PFLOP/s dense bf16 MFMA peak. One JSON line per T,
+then a summary line.
 """
 
 import argparse
@@ -24,11 +28,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(
     os.path.abspath(__file__))))
 
 PEAK_GBS = 8000.0
+PEAK_TFLOPS = 2500.0
 
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--tokens", type=int, nargs="+", default=[1, 8, 32, 64])
+    p.add_argument("--tokens", type=int, nargs="+",
+                   default=[1, 8, 32, 64, 128, 256, 1024, 4096])
+    p.add_argument("--path", nargs="+", choices=["stream", "tiled"],
+                   default=["stream", "tiled"],
+                   help="the fused paths to run next to the eager block")
+    p.add_argument("--no-eager", action="store_true")
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--iters", type=int, default=200)
     p.add_argument("--hidden", type=int, default=4096)
@@ -65,41 +75,54 @@ def main():
         end.synchronize()
         return beg.elapsed_time(end) / args.iters  # ms per call
 
-    all_faster = True
+    fused_faster = {}
     with torch.no_grad():
         for T in args.tokens:
             x = torch.randn(T, 1, args.hidden, device=dev).to(torch.bfloat16)
             logits = layer.router(x.reshape(T, -1)).float()
             hit = int(K.moe_route(logits, args.top_k)[0].unique().numel())
-            ref, out = layer(x).float(), layer.decode(x).float()
-            rel = float((out - ref).norm() / ref.norm())
+            fns = {} if args.no_eager else {"eager": layer}
+            for path in args.path:
+                if path == "tiled" or \
+                        T * args.top_k <= K.MOE_STREAM_MAX_ENTRIES:
+                    fns[path] = lambda x, path=path: layer.decode(x, path)
+            ref = layer(x).float()
+            rel = {n: float((fn(x).float() - ref).norm() / ref.norm())
+                   for n, fn in fns.items() if n != "eager"}
             for _ in range(3):
-                layer(x)
-                layer.decode(x)
+                for fn in fns.values():
+                    fn(x)
             torch.cuda.synchronize()
-            runs = {"eager": [], "fused": []}
+            runs = {n: [] for n in fns}
             for _ in range(args.rounds):
-                runs["eager"].append(timed(layer, x))
-                runs["fused"].append(timed(layer.decode, x))
-            faster = max(runs["fused"]) < min(runs["eager"])
-            all_faster &= faster
-            gbs = {n: [hit * expert_bytes / (ms * 1e-3) / 1e9 for ms in v]
-                   for n, v in runs.items()}
-            print(json.dumps({
-                "T": T, "experts_hit": hit,
-                "weight_bytes": hit * expert_bytes,
-                "eager_ms": [round(v, 4) for v in runs["eager"]],
-                "fused_ms": [round(v, 4) for v in runs["fused"]],
-                "eager_GBs": [round(v, 1) for v in gbs["eager"]],
-                "fused_GBs": [round(v, 1) for v in gbs["fused"]],
-                "fused_peak_share": round(max(gbs["fused"]) / PEAK_GBS, 3),
-                "every_fused_run_faster": faster,
-                "fused_vs_eager_rel_l2": round(rel, 5),
-            }), flush=True)
+                for n, fn in fns.items():
+                    runs[n].append(timed(fn, x))
+            flops = 6.0 * T * args.top_k * args.hidden * args.inter
+            line = {"T": T, "experts_hit": hit,
+                    "weight_bytes": hit * expert_bytes, "flops": flops}
+            for n, v in runs.items():
+                line[n + "_ms"] = [round(ms, 4) for ms in v]
+                line[n + "_GBs"] = [
+                    round(hit * expert_bytes / (ms * 1e-3) / 1e9, 1)
+                    for ms in v]
+                line[n + "_TFLOPs"] = [round(flops / (ms * 1e-3) / 1e12, 1)
+                                       for ms in v]
+                if n != "eager":
+                    line[n + "_peak_GBs_share"] = round(
+                        max(line[n + "_GBs"]) / PEAK_GBS, 3)
+                    line[n + "_peak_TFLOPs_share"] = round(
+                        max(line[n + "_TFLOPs"]) / PEAK_TFLOPS, 3)
+                    line[n + "_vs_eager_rel_l2"] = round(rel[n], 5)
+                    if "eager" in runs:
+                        faster = max(v) < min(runs["eager"])
+                        line["every_%s_run_faster" % n] = faster
+                        fused_faster.setdefault(n, []).append((T, faster))
+            print(json.dumps(line), flush=True)
     print(json.dumps({
-        "metric": "MoE block, fused vs eager decode",
-        "every_fused_run_faster_at_every_T": all_faster,
-        "peak_GBs": PEAK_GBS,
+        "metric": "MoE block, fused (stream, tiled) vs eager",
+        "every_run_faster_than_every_eager_run_at_T": {
+            n: {str(T): f for T, f in v} for n, v in fused_faster.items()},
+        "peak_GBs": PEAK_GBS, "peak_TFLOPs": PEAK_TFLOPS,
         "config": {"hidden": args.hidden, "inter": args.inter,
                    "experts": args.experts, "top_k": args.top_k,
                    "rounds": args.rounds, "iters": args.iters},

@@ -38,6 +38,11 @@ class MixtralConfig:
     # decode_step runs the MoE block through the fused device-routed
     # kernels (ops/csrc/moe.hip): no host read, hipGraph-capturable
     fused_moe_decode: bool = False
+    # forward (prefill, verify blocks, generate's prompt pass) runs the MoE
+    # block through the same fused call when no grad is required and there
+    # is no expert parallelism; large batches take the tiled kernels of
+    # ops/csrc/moe_prefill.hip
+    fused_moe_prefill: bool = False
 
     @classmethod
     def mixtral_8x7b(cls):
@@ -165,11 +170,46 @@ class MoELayer(nn.Module):
             for p in self.local_experts.parameters():
                 p._mfx_no_sync = True
 
+    # forward's fused block, chosen from shapes by the mean expert run
+    # T * top_k / E. Up to TILED_MEAN_RUN entries the stream kernels: they
+    # serve an expert in groups of 32 entries and read its weights again
+    # for every further group, and at 8x7B geometry they win up to a mean
+    # run of 28 and lose from 30 on, where some expert passes 32. Above
+    # that the tiled kernels, up to TILED_MAX_MEAN_RUN: measured faster
+    # than the eager block up to a mean run of 384 and slower from 512 on
+    # (docs/KERNELS.md, "MoE prefill"), so larger batches stay eager.
+    TILED_MEAN_RUN = 28
+    TILED_MAX_MEAN_RUN = 384
+
+    def _fused_path(self, T):
+        """"stream", "tiled" or None (the eager block) for T tokens."""
+        run = T * self.cfg.top_k
+        E = self.cfg.num_experts
+        if run <= self.TILED_MEAN_RUN * E and \
+                run <= K.MOE_STREAM_MAX_ENTRIES:
+            return "stream"
+        if run <= self.TILED_MAX_MEAN_RUN * E and run <= K.MOE_MAX_ENTRIES:
+            return "tiled"
+        return None
+
+    def _wants_grad(self, x):
+        return torch.is_grad_enabled() and (
+            x.requires_grad or any(p.requires_grad
+                                   for p in self.parameters()))
+
     def forward(self, x):
         cfg = self.cfg
+        if (cfg.fused_moe_prefill and self.ep_world == 1
+                and not self._wants_grad(x)):
+            path = self._fused_path(x.numel() // x.size(-1))
+            if path is not None:
+                return self.decode(x, path)
         B, S, h = x.shape
         flat = x.reshape(B * S, h)
         logits = self.router(flat).float()
+        # softmax over all experts, top-k, renormalise: the same weights as
+        # the fused block's softmax over the selected logits, since the
+        # normaliser of the full softmax cancels in the renormalisation
         probs = torch.softmax(logits, dim=-1)
         weights, experts = probs.topk(cfg.top_k, dim=-1)  # [N, k]
         weights = weights / weights.sum(-1, keepdim=True)
@@ -246,12 +286,14 @@ class MoELayer(nn.Module):
         out.index_add_(0, token_idx, contrib)
         return out.reshape(B, S, h)
 
-    def decode(self, x):
-        """The block at decode time, inference-only and without EP: the
-        router GEMM, then K.moe_ffn (device routing, grouped expert
-        kernels). Reads nothing back, unlike forward's per-expert counts.
-        The table of weight addresses is cached and rebuilt when a weight
-        has moved (a host-side comparison of data_ptr()s)."""
+    def decode(self, x, path="stream"):
+        """The fused block, inference-only and without EP: the router
+        GEMM, then K.moe_ffn (device routing, grouped expert kernels) on
+        ``path``: the stream kernels at decode, and from forward with
+        cfg.fused_moe_prefill whichever the batch size calls for. Reads
+        nothing back, unlike forward's per-expert counts. The table of
+        weight addresses is cached and rebuilt when a weight has moved (a
+        host-side comparison of data_ptr()s)."""
         assert self.ep_world == 1, "fused MoE decode has no EP path"
         B, S, h = x.shape
         flat = x.reshape(B * S, h)
@@ -262,7 +304,10 @@ class MoELayer(nn.Module):
         table = getattr(self, "_moe_table", None)
         if table is None or table.ptrs != K.MoeTable.addresses(*ws):
             table = self._moe_table = K.MoeTable(*ws)
-        out = K.moe_ffn(flat, logits, table, top_k=self.cfg.top_k)
+        if flat.size(0) * self.cfg.top_k > K.MOE_STREAM_MAX_ENTRIES:
+            path = "tiled"
+        out = K.moe_ffn(flat, logits, table, top_k=self.cfg.top_k,
+                        path=path)
         return out.reshape(B, S, h)
 
 

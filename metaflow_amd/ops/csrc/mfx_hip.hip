@@ -18,6 +18,7 @@
 #include "append_fp8.hip"
 #include "sampling.hip"
 #include "moe.hip"
+#include "moe_prefill.hip"
 #include "debug_kernels.hip"
 
 namespace {
@@ -874,35 +875,79 @@ torch::Tensor sample_tokens(torch::Tensor logits, torch::Tensor temperature,
 }
 
 // ----------------------------------------------------------------- MoE
-// Decode-time MoE feed-forward (moe.hip). Nothing is read on the host.
-// {expert [T,k] i32, weight [T,k] f32, order [T*k] i32, offset [E+1] i32,
-//  slot [T*k] i32 (the inverse of order)}
-std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t k) {
+// MoE feed-forward (moe.hip, moe_prefill.hip). Nothing is read on the host.
+struct MoeRoute {
+  torch::Tensor expert, weight, order, offset, slot;  // as moe_route returns
+  torch::Tensor tiles;  // wide route only: int32 [max_tiles, 2]
+};
+
+// M tiles of the tiled GEMMs, bounded from shapes alone: sum_e ceil(n_e /
+// TM) <= entries / TM + (experts that can hold a ragged tile).
+long long moep_max_tiles(long long E, long long entries) {
+  return entries / MOEP_TM + std::min(E, entries);
+}
+
+// wide = false: moe_route_kernel, one workgroup, T * k <= 2048.
+// wide = true: the three launches of moe_prefill.hip, T * k <= 65536, and
+// the tile map.
+MoeRoute moe_route_impl(torch::Tensor logits, int64_t k, bool wide) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 &&
               logits.scalar_type() == torch::kFloat32 &&
               logits.is_contiguous(),
               "logits must be contiguous fp32 [T, E] on GPU");
   const long long T = logits.size(0), E = logits.size(1);
+  const long long cap = wide ? MOEP_MAX_ENTRIES : MOE_MAX_ENTRIES;
   TORCH_CHECK(E >= 1 && E <= MOE_MAX_E, "moe_route needs 1 <= E <= ",
               MOE_MAX_E, ", got ", E);
   TORCH_CHECK(k >= 1 && k <= MOE_MAX_K && k <= E,
               "moe_route needs 1 <= top_k <= min(E, ", MOE_MAX_K, "), got ",
               k);
-  TORCH_CHECK(T >= 1 && T * k <= MOE_MAX_ENTRIES,
-              "moe_route needs 1 <= T * top_k <= ", MOE_MAX_ENTRIES,
-              ", got T = ", T);
+  TORCH_CHECK(T >= 1 && T * k <= cap,
+              "moe_route needs 1 <= T * top_k <= ", cap, ", got T = ", T);
   auto i32 = logits.options().dtype(torch::kInt32);
-  auto expert = torch::empty({T, k}, i32);
-  auto weight = torch::empty({T, k}, logits.options());
-  auto order = torch::empty({T * k}, i32);
-  auto offset = torch::empty({E + 1}, i32);
-  auto slot = torch::empty({T * k}, i32);
-  moe_route_kernel<<<1, MOE_ROUTE_BLOCK, 0, cur_stream()>>>(
+  MoeRoute r;
+  r.expert = torch::empty({T, k}, i32);
+  r.weight = torch::empty({T, k}, logits.options());
+  r.order = torch::empty({T * k}, i32);
+  r.offset = torch::empty({E + 1}, i32);
+  r.slot = torch::empty({T * k}, i32);
+  if (!wide) {
+    moe_route_kernel<<<1, MOE_ROUTE_BLOCK, 0, cur_stream()>>>(
+        logits.data_ptr<float>(), (int)T, (int)E, (int)k,
+        r.expert.data_ptr<int>(), r.weight.data_ptr<float>(),
+        r.order.data_ptr<int>(), r.offset.data_ptr<int>(),
+        r.slot.data_ptr<int>());
+    HIP_CHECK_KERNEL();
+    return r;
+  }
+  const long long nb = (T + MOEP_RT - 1) / MOEP_RT;
+  const long long max_tiles = moep_max_tiles(E, T * k);
+  auto cnt = torch::empty({nb, E}, i32);
+  r.tiles = torch::empty({max_tiles, 2}, i32);
+  moep_topk_kernel<<<(int)nb, MOEP_RT, 0, cur_stream()>>>(
       logits.data_ptr<float>(), (int)T, (int)E, (int)k,
-      expert.data_ptr<int>(), weight.data_ptr<float>(),
-      order.data_ptr<int>(), offset.data_ptr<int>(), slot.data_ptr<int>());
+      r.expert.data_ptr<int>(), r.weight.data_ptr<float>(),
+      r.slot.data_ptr<int>(), cnt.data_ptr<int>());
   HIP_CHECK_KERNEL();
-  return {expert, weight, order, offset, slot};
+  moep_scan_kernel<<<1, WAVE, 0, cur_stream()>>>(
+      cnt.data_ptr<int>(), (int)nb, (int)E, (int)max_tiles,
+      r.offset.data_ptr<int>(),
+      reinterpret_cast<int2*>(r.tiles.data_ptr<int>()));
+  HIP_CHECK_KERNEL();
+  moep_scatter_kernel<<<(int)nb, MOEP_RT, 0, cur_stream()>>>(
+      r.expert.data_ptr<int>(), cnt.data_ptr<int>(),
+      r.offset.data_ptr<int>(), (int)T, (int)E, (int)k,
+      r.order.data_ptr<int>(), r.slot.data_ptr<int>());
+  HIP_CHECK_KERNEL();
+  return r;
+}
+
+// {expert [T,k] i32, weight [T,k] f32, order [T*k] i32, offset [E+1] i32,
+//  slot [T*k] i32 (the inverse of order)}
+std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t k,
+                                     bool wide) {
+  const MoeRoute r = moe_route_impl(logits, k, wide);
+  return {r.expert, r.weight, r.order, r.offset, r.slot};
 }
 
 // Split-K of the down projection, from shapes alone: enough blocks to
@@ -924,12 +969,30 @@ int moe_down_splits(long long E, long long entries, long long hidden,
       1, std::min<long long>({want, inter / MOE_KC, 16ll}));
 }
 
+// out[t] = sum_j weight[t, j] * sum_split y[split, slot[t*k + j]]. The
+// kernel takes its token from grid.y: launched in runs of 32768 tokens.
+void moe_combine(const torch::Tensor& y, const MoeRoute& r,
+                 torch::Tensor& out, long long T, long long k,
+                 long long splits, long long hidden) {
+  for (long long t0 = 0; t0 < T; t0 += 32768) {
+    const long long nt = std::min(T - t0, 32768ll);
+    moe_combine_kernel<<<dim3((hidden + 1023) / 1024, nt), 256, 0,
+                         cur_stream()>>>(
+        y.data_ptr<float>(), r.weight.data_ptr<float>() + t0 * k,
+        r.slot.data_ptr<int>() + t0 * k, bfm(out) + t0 * hidden, (int)k,
+        (int)splits, (int)(T * k), (int)hidden);
+    HIP_CHECK_KERNEL();
+  }
+}
+
 // x [T, hidden] bf16, logits [T, E] fp32, tab int64 [3, E] device table of
 // the gate / up / down weight addresses ([inter, hidden] x2, [hidden,
 // inter], bf16, 16-byte aligned) -> out [T, hidden] bf16.
+// tiled = false: the weight-stream kernels of moe.hip (decode); tiled =
+// true: wide route and the tiled GEMMs of moe_prefill.hip (splits unused).
 torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
                       torch::Tensor tab, int64_t k, int64_t inter,
-                      int64_t splits) {
+                      int64_t splits, bool tiled) {
   check_bf16(x, "x");
   TORCH_CHECK(x.dim() == 2 && logits.dim() == 2 &&
               logits.size(0) == x.size(0),
@@ -945,33 +1008,47 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
               "tab must be a contiguous int64 [3, E] table on GPU");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
               "x must be 16-byte aligned");
-  auto r = moe_route(logits, k);
+  const MoeRoute r = moe_route_impl(logits, k, tiled);
   const long long entries = T * k;
+  auto h = torch::empty({entries, inter}, x.options());
+  auto out = torch::empty_like(x);
+  const long long* tp =
+      reinterpret_cast<const long long*>(tab.data_ptr<int64_t>());
+  if (tiled) {
+    const unsigned tiles = (unsigned)r.tiles.size(0);
+    const int2* tm = reinterpret_cast<const int2*>(r.tiles.data_ptr<int>());
+    auto y = torch::empty({entries, hidden},
+                          x.options().dtype(torch::kFloat32));
+    moep_gateup_kernel<<<dim3(tiles, inter / MOEP_TN), MOEP_BLOCK, 0,
+                         cur_stream()>>>(
+        bf(x), tp, r.order.data_ptr<int>(), r.offset.data_ptr<int>(), tm,
+        bfm(h), (int)E, (int)k, (int)hidden, (int)inter);
+    HIP_CHECK_KERNEL();
+    moep_dn_kernel<<<dim3(tiles, hidden / MOEP_TN), MOEP_BLOCK, 0,
+                     cur_stream()>>>(
+        bf(h), tp, r.offset.data_ptr<int>(), tm, y.data_ptr<float>(),
+        (int)E, (int)hidden, (int)inter);
+    HIP_CHECK_KERNEL();
+    moe_combine(y, r, out, T, k, 1, hidden);
+    return out;
+  }
   const long long nc = inter / MOE_KC;
   if (splits <= 0) splits = moe_down_splits(E, entries, hidden, inter);
   TORCH_CHECK(splits <= nc && splits <= 64,
               "down_splits must be at most inter / 128 and 64");
-  auto h = torch::empty({entries, inter}, x.options());
   auto y = torch::empty({splits, entries, hidden},
                         x.options().dtype(torch::kFloat32));
-  auto out = torch::empty_like(x);
-  const long long* tp =
-      reinterpret_cast<const long long*>(tab.data_ptr<int64_t>());
   moe_gate_up_kernel<<<dim3(inter / MOE_ROWS, E), MOE_BLOCK, 0,
                        cur_stream()>>>(
-      bf(x), tp, r[2].data_ptr<int>(), r[3].data_ptr<int>(), bfm(h), (int)E,
-      (int)k, (int)hidden, (int)inter);
+      bf(x), tp, r.order.data_ptr<int>(), r.offset.data_ptr<int>(), bfm(h),
+      (int)E, (int)k, (int)hidden, (int)inter);
   HIP_CHECK_KERNEL();
   moe_down_kernel<<<dim3(hidden / MOE_ROWS, E, splits), MOE_BLOCK, 0,
                     cur_stream()>>>(
-      bf(h), tp, r[3].data_ptr<int>(), y.data_ptr<float>(), (int)E,
+      bf(h), tp, r.offset.data_ptr<int>(), y.data_ptr<float>(), (int)E,
       (int)entries, (int)hidden, (int)inter);
   HIP_CHECK_KERNEL();
-  moe_combine_kernel<<<dim3((hidden + 1023) / 1024, T), 256, 0,
-                       cur_stream()>>>(
-      y.data_ptr<float>(), r[1].data_ptr<float>(), r[4].data_ptr<int>(),
-      bfm(out), (int)k, (int)splits, (int)entries, (int)hidden);
-  HIP_CHECK_KERNEL();
+  moe_combine(y, r, out, T, k, splits, hidden);
   return out;
 }
 
@@ -1079,12 +1156,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "top_k, top_p, u -> int64 [B] token ids (temperature <= 0 = "
         "argmax)");
   m.def("moe_route", &moe_route,
-        "MoE routing on the device: logits fp32 [T,E], top_k -> expert, "
-        "weight, order, offset, slot");
+        "MoE routing on the device: logits fp32 [T,E], top_k, wide (the "
+        "multi-block route, T * top_k <= 65536) -> expert, weight, order, "
+        "offset, slot");
   m.def("moe_ffn", &moe_ffn,
-        "decode-time MoE feed-forward: x [T,hidden], logits fp32 [T,E], "
-        "int64 [3,E] weight address table, top_k, inter, down splits "
-        "(<= 0 = from shapes) -> [T,hidden]");
+        "MoE feed-forward: x [T,hidden], logits fp32 [T,E], int64 [3,E] "
+        "weight address table, top_k, inter, down splits (<= 0 = from "
+        "shapes), tiled (the prefill kernels) -> [T,hidden]");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");

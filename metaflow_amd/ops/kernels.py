@@ -979,7 +979,9 @@ def sample_tokens(logits, temperature, top_k, top_p, u):
 # ================================= MoE =====================================
 MOE_MAX_EXPERTS = 64
 MOE_MAX_TOP_K = 8
-MOE_MAX_ENTRIES = 2048
+MOE_MAX_ENTRIES = 65536
+# the one-workgroup route and the weight-stream kernels of moe.hip end here
+MOE_STREAM_MAX_ENTRIES = 2048
 
 
 def _moe_check_route(T, E, top_k):
@@ -1023,17 +1025,25 @@ def moe_route_ref(logits, top_k):
             offset.to(torch.int32))
 
 
-def moe_route(logits, top_k):
+def moe_route(logits, top_k, wide=None):
     """Top-k routing of [T, E] fp32 router logits, see moe_route_ref.
 
-    GPU -> moe.hip (one small workgroup, no atomics, nothing read on the
-    host). CPU -> moe_route_ref. Inference-only."""
+    GPU -> moe.hip (one small workgroup) where T * top_k <= 2048, above
+    that, or with ``wide=True``, the multi-block route of moe_prefill.hip
+    (T * top_k <= 65536); both without atomics and with nothing read on
+    the host. CPU -> moe_route_ref. Inference-only."""
     _moe_no_grad(logits)
     if not logits.is_cuda:
         return moe_route_ref(logits, top_k)
-    _moe_check_route(logits.size(0), logits.size(1), top_k)
+    T = logits.size(0)
+    _moe_check_route(T, logits.size(1), top_k)
+    if wide is None:
+        wide = T * top_k > MOE_STREAM_MAX_ENTRIES
+    elif not wide and T * top_k > MOE_STREAM_MAX_ENTRIES:
+        raise ValueError("the one-workgroup route needs T * top_k <= %d"
+                         % MOE_STREAM_MAX_ENTRIES)
     return tuple(hip_ext().moe_route(logits.float().contiguous(),
-                                     top_k)[:4])
+                                     top_k, bool(wide))[:4])
 
 
 class MoeTable(object):
@@ -1097,18 +1107,23 @@ def moe_ffn_ref(x, logits, w_gate, w_up, w_down, top_k,
 
 
 def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
-            down_splits=None):
-    """Decode-time MoE feed-forward: x [T, hidden] bf16 and the router's
-    fp32 logits [T, E] -> [T, hidden] in x's dtype.
+            down_splits=None, path=None):
+    """Fused MoE feed-forward: x [T, hidden] bf16 and the router's fp32
+    logits [T, E] -> [T, hidden] in x's dtype.
 
     w_gate, w_up, w_down: sequences of E weights ([inter, hidden] twice,
     [hidden, inter]), or a prebuilt MoeTable as w_gate alone. hidden and
-    inter must be multiples of 128; E <= 64, top_k <= 8, T * top_k <= 2048.
-    down_splits: split-K of the down projection; None picks it from the
-    shapes and the CU count (never from the routing).
+    inter must be multiples of 128; E <= 64, top_k <= 8, T * top_k <= 65536.
+    path: "stream" -> moe.hip, the decode kernels that stream an expert's
+    weights once per 32 entries (T * top_k <= 2048); "tiled" ->
+    moe_prefill.hip, the prefill kernels (multi-block route, 128 x 128
+    tiles through LDS; any T); None -> "stream" where it accepts the
+    shape, "tiled" above.
+    down_splits: split-K of the stream path's down projection; None picks
+    it from the shapes and the CU count (never from the routing).
 
-    GPU -> moe.hip: route, gate/up + SwiGLU, down, combine: four launches,
-    nothing read on the host, no atomics, so the call is deterministic and
+    Either path: route, gate/up + SwiGLU, down, combine, with nothing read
+    on the host and no atomics, so the call is deterministic and
     hipGraph-capturable. CPU -> moe_ffn_ref. Inference-only."""
     table = w_gate if isinstance(w_gate, MoeTable) else \
         MoeTable(w_gate, w_up, w_down)
@@ -1119,6 +1134,15 @@ def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
         raise ValueError("moe_ffn: x must be [T, %d] and logits [T, %d]"
                          % (table.hidden, len(table.weights[0])))
     _moe_check_route(T, logits.size(1), top_k)
+    if path not in (None, "stream", "tiled"):
+        raise ValueError('moe_ffn: path must be None, "stream" or "tiled"')
+    if path is None:
+        path = "stream" if T * top_k <= MOE_STREAM_MAX_ENTRIES else "tiled"
+    elif path == "stream" and T * top_k > MOE_STREAM_MAX_ENTRIES:
+        raise ValueError("moe_ffn: the stream path needs T * top_k <= %d"
+                         % MOE_STREAM_MAX_ENTRIES)
+    if path == "tiled" and down_splits is not None:
+        raise ValueError("moe_ffn: down_splits applies to the stream path")
     if not x.is_cuda:
         return moe_ffn_ref(x, logits, *table.weights, top_k).to(x.dtype)
     if down_splits is not None and not \
@@ -1126,7 +1150,7 @@ def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
         raise ValueError("down_splits must be in [1, min(inter / 128, 64)]")
     return hip_ext().moe_ffn(x.contiguous(), logits.float().contiguous(),
                              table.tab, top_k, table.inter,
-                             down_splits or 0)
+                             down_splits or 0, path == "tiled")
 
 
 # ================================ adam =====================================
