@@ -15,7 +15,9 @@ straight over the cache allocation; prefill runs the flash fwd kernel.
 continuous batcher over --batch requests of --new tokens with the eager MoE
 block, with the fused block (cfg.fused_moe_decode, ops/csrc/moe.hip) run
 eagerly, and with the fused block replayed from a captured hipGraph, which
-only the fused block allows.
+only the fused block allows. With --fp8-experts a copy of the model with
+quantised experts (MixtralForCausalLM.quantize_experts_, E4M3 weights and
+row scales) joins the same rounds, fused eagerly and from a graph.
 
 --fused-moe-prefill (mixtral-tiny) keeps the fused decode block and graph
 replay in both contestants and switches the prefill's MoE block: eager
@@ -56,14 +58,24 @@ def fused_moe_serving(args, device):
     prompts = [torch.randint(0, cfg.vocab_size, (prompt_len,),
                              generator=g).tolist()
                for _ in range(args.batch)]
-    modes = {"eager_moe": (False, False), "fused_moe": (True, False),
-             "fused_moe_graph": (True, True)}
+    modes = {"eager_moe": (False, False, model),
+             "fused_moe": (True, False, model),
+             "fused_moe_graph": (True, True, model)}
+    if args.fp8_experts:
+        import copy
+
+        qmodel = copy.deepcopy(model).quantize_experts_()
+        qmodel.cfg = cfg  # one config object switches both models
+        for layer in qmodel.layers:
+            layer.cfg = layer.moe.cfg = cfg
+        modes["fused_moe_fp8"] = (True, False, qmodel)
+        modes["fused_moe_fp8_graph"] = (True, True, qmodel)
     runs = {name: [] for name in modes}
     tokens = {}
     for rnd in range(4):  # round 0 warms up
-        for name, (fused, graph) in modes.items():
+        for name, (fused, graph, mdl) in modes.items():
             cfg.fused_moe_decode = fused
-            b = ContinuousBatcher(model, max_batch=args.batch,
+            b = ContinuousBatcher(mdl, max_batch=args.batch,
                                   max_len=prompt_len + args.new + 64,
                                   graph=graph)
             reqs = [b.submit(pr, args.new) for pr in prompts]
@@ -86,6 +98,9 @@ def fused_moe_serving(args, device):
         tokens["eager_moe"],
         "graph_same_tokens_as_fused": tokens["fused_moe_graph"] ==
         tokens["fused_moe"],
+        "fp8_graph_same_tokens_as_fp8_fused":
+            tokens["fused_moe_fp8_graph"] == tokens["fused_moe_fp8"]
+            if args.fp8_experts else None,
         "config": {"model": args.model, "batch": args.batch,
                    "prompt": prompt_len, "new": args.new,
                    "device": str(device)},
@@ -155,6 +170,9 @@ def main():
     p.add_argument("--fused-moe", action="store_true",
                    help="mixtral-tiny: serving decode, eager MoE vs fused "
                         "MoE (eager and graph replay)")
+    p.add_argument("--fp8-experts", action="store_true",
+                   help="--fused-moe: add the fused block over quantised "
+                        "(E4M3) experts to the rounds")
     p.add_argument("--fused-moe-prefill", action="store_true",
                    help="mixtral-tiny: serving with the eager vs the fused "
                         "MoE block at prefill")

@@ -6,7 +6,8 @@ decode kernels, T * top_k <= 2048) and "tiled" (moe_prefill.hip, the
 prefill kernels).
 
     python benchmarks/bench_moe.py [--tokens 1 8 32 64 128 256 1024 4096]
-        [--path stream tiled] [--rounds 3] [--iters 200]
+        [--path stream tiled] [--expert-dtype bf16 fp8] [--rounds 3]
+        [--iters 200]
 
 Mixtral 8x7B geometry by default (hidden 4096, inter 14336, E = 8, k = 2).
 Per T the contestants alternate for --rounds rounds; a run is --iters calls
@@ -17,9 +18,17 @@ over the time of one call, next to the 8 TB/s HBM peak of the MI355X. The
 FLOPs are those of the routed entries, 6 * T * top_k * hidden * inter;
 TFLOP/s next to the 2.5 PFLOP/s dense bf16 MFMA peak. One JSON line per T,
 then a summary line.
+
+--expert-dtype fp8 quantises the experts (MoELayer.quantize_experts_: E4M3
+bytes and one fp32 scale per weight row); given both, a bf16 and a
+quantised copy of the layer alternate in the same rounds and the fp8
+contestants carry the suffix _fp8 (their eager block is the dequantising
+fallback). A contestant's bytes are the bytes it stores: E4M3 bytes plus
+scales for fp8.
 """
 
 import argparse
+import copy
 import json
 import os
 import sys
@@ -39,6 +48,8 @@ def main():
                    default=["stream", "tiled"],
                    help="the fused paths to run next to the eager block")
     p.add_argument("--no-eager", action="store_true")
+    p.add_argument("--expert-dtype", nargs="+", choices=["bf16", "fp8"],
+                   default=["bf16"])
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--iters", type=int, default=200)
     p.add_argument("--hidden", type=int, default=4096)
@@ -63,7 +74,14 @@ def main():
     for prm in layer.parameters():
         torch.nn.init.normal_(prm, std=0.02)
     layer.eval()
-    expert_bytes = 3 * args.hidden * args.inter * 2
+    # contestant suffix: (layer, stored bytes of one expert)
+    layers = {}
+    if "bf16" in args.expert_dtype:
+        layers[""] = (layer, 3 * args.hidden * args.inter * 2)
+    if "fp8" in args.expert_dtype:
+        qlayer = copy.deepcopy(layer).quantize_experts_()
+        layers["_fp8"] = (qlayer, 3 * args.hidden * args.inter +
+                          4 * (2 * args.inter + args.hidden))
 
     def timed(fn, x):
         beg = torch.cuda.Event(enable_timing=True)
@@ -81,11 +99,17 @@ def main():
             x = torch.randn(T, 1, args.hidden, device=dev).to(torch.bfloat16)
             logits = layer.router(x.reshape(T, -1)).float()
             hit = int(K.moe_route(logits, args.top_k)[0].unique().numel())
-            fns = {} if args.no_eager else {"eager": layer}
-            for path in args.path:
-                if path == "tiled" or \
-                        T * args.top_k <= K.MOE_STREAM_MAX_ENTRIES:
-                    fns[path] = lambda x, path=path: layer.decode(x, path)
+            fns, nbytes = {}, {}
+            for sfx, (lay, eb) in layers.items():
+                if not args.no_eager:
+                    fns["eager" + sfx] = lay
+                for path in args.path:
+                    if path == "tiled" or \
+                            T * args.top_k <= K.MOE_STREAM_MAX_ENTRIES:
+                        fns[path + sfx] = \
+                            lambda x, path=path, lay=lay: lay.decode(x, path)
+                for n in fns:
+                    nbytes.setdefault(n, hit * eb)
             ref = layer(x).float()
             rel = {n: float((fn(x).float() - ref).norm() / ref.norm())
                    for n, fn in fns.items() if n != "eager"}
@@ -99,12 +123,12 @@ def main():
                     runs[n].append(timed(fn, x))
             flops = 6.0 * T * args.top_k * args.hidden * args.inter
             line = {"T": T, "experts_hit": hit,
-                    "weight_bytes": hit * expert_bytes, "flops": flops}
+                    "weight_bytes": nbytes[next(iter(fns))], "flops": flops}
             for n, v in runs.items():
                 line[n + "_ms"] = [round(ms, 4) for ms in v]
+                line[n + "_weight_bytes"] = nbytes[n]
                 line[n + "_GBs"] = [
-                    round(hit * expert_bytes / (ms * 1e-3) / 1e9, 1)
-                    for ms in v]
+                    round(nbytes[n] / (ms * 1e-3) / 1e9, 1) for ms in v]
                 line[n + "_TFLOPs"] = [round(flops / (ms * 1e-3) / 1e12, 1)
                                        for ms in v]
                 if n != "eager":
@@ -117,6 +141,9 @@ def main():
                         faster = max(v) < min(runs["eager"])
                         line["every_%s_run_faster" % n] = faster
                         fused_faster.setdefault(n, []).append((T, faster))
+                    if n.endswith("_fp8") and n[:-4] in runs:
+                        line["every_%s_run_below_bf16" % n] = \
+                            max(v) < min(runs[n[:-4]])
             print(json.dumps(line), flush=True)
     print(json.dumps({
         "metric": "MoE block, fused (stream, tiled) vs eager",

@@ -137,6 +137,49 @@ class Expert(nn.Module):
         return self.down_proj(K.swiglu(self.gate_proj(x), self.up_proj(x)))
 
 
+class Fp8Expert(nn.Module):
+    """An Expert with weight-only FP8 weights: E4M3 bytes and one fp32
+    scale per output row (K.moe_quant_weight), held as buffers, so
+    state_dict round-trips and there is nothing to train. The fused MoE
+    block reads bytes and scales as they are (K.MoeTable with scales);
+    ``forward`` is the eager fallback for the CPU, expert parallelism and
+    batches above the fused thresholds: dequantise to bf16, then Expert's
+    GEMMs and K.swiglu. It is differentiable in x."""
+
+    NAMES = ("gate_proj", "up_proj", "down_proj")
+
+    def __init__(self, hidden, inter, device=None):
+        super().__init__()
+        for name, (dout, din) in zip(self.NAMES, ((inter, hidden),
+                                                  (inter, hidden),
+                                                  (hidden, inter))):
+            self.register_buffer(name + "_w8", torch.zeros(
+                dout, din, dtype=torch.float8_e4m3fn, device=device))
+            self.register_buffer(name + "_scale", torch.ones(
+                dout, dtype=torch.float32, device=device))
+
+    @classmethod
+    def from_expert(cls, expert):
+        w = expert.gate_proj.weight
+        q = cls(w.size(1), w.size(0), device=w.device)
+        for name in cls.NAMES:
+            w8, scale = K.moe_quant_weight(getattr(expert, name).weight)
+            getattr(q, name + "_w8").copy_(w8)
+            getattr(q, name + "_scale").copy_(scale)
+        return q
+
+    def weight(self, name, dtype=torch.bfloat16):
+        return K.moe_dequant_ref(getattr(self, name + "_w8"),
+                                 getattr(self, name + "_scale"), dtype)
+
+    def forward(self, x):
+        from ..ops.gemm import tuned_linear
+
+        g = tuned_linear(x, self.weight("gate_proj", x.dtype))
+        u = tuned_linear(x, self.weight("up_proj", x.dtype))
+        return tuned_linear(K.swiglu(g, u), self.weight("down_proj", x.dtype))
+
+
 class MoELayer(nn.Module):
     """Top-k router + (optionally expert-parallel) experts.
 
@@ -180,17 +223,67 @@ class MoELayer(nn.Module):
     # (docs/KERNELS.md, "MoE prefill"), so larger batches stay eager.
     TILED_MEAN_RUN = 28
     TILED_MAX_MEAN_RUN = 384
+    # Quantised experts (docs/KERNELS.md, "FP8 expert weights"): the E4M3
+    # stream reads half the bytes per group and the tiled kernels, bound by
+    # LDS, gain nothing from them, so the stream wins up to a mean run of 48
+    # (every run, also past the second group) and loses from 64 on. The
+    # eager block here is the dequantising fallback, which rewrites every
+    # expert in bf16 per call: the tiled kernels won at every size
+    # measured, up to a mean run of 1024.
+    TILED_MEAN_RUN_FP8 = 48
+    TILED_MAX_MEAN_RUN_FP8 = 1024
 
     def _fused_path(self, T):
         """"stream", "tiled" or None (the eager block) for T tokens."""
         run = T * self.cfg.top_k
         E = self.cfg.num_experts
-        if run <= self.TILED_MEAN_RUN * E and \
+        q = self.quantized
+        if run <= (self.TILED_MEAN_RUN_FP8 if q
+                   else self.TILED_MEAN_RUN) * E and \
                 run <= K.MOE_STREAM_MAX_ENTRIES:
             return "stream"
-        if run <= self.TILED_MAX_MEAN_RUN * E and run <= K.MOE_MAX_ENTRIES:
+        if run <= (self.TILED_MAX_MEAN_RUN_FP8 if q
+                   else self.TILED_MAX_MEAN_RUN) * E and \
+                run <= K.MOE_MAX_ENTRIES:
             return "tiled"
         return None
+
+    @property
+    def quantized(self):
+        return len(self.local_experts) > 0 and all(
+            isinstance(e, Fp8Expert) for e in self.local_experts)
+
+    @torch.no_grad()
+    def quantize_experts_(self):
+        """Replace every Expert by an Fp8Expert of its weights (E4M3 bytes,
+        one scale per output row) and free the bf16 parameters. The fused
+        block then streams half the bytes; training through quantised
+        experts is not supported (they have no parameters)."""
+        for i, e in enumerate(self.local_experts):
+            if not isinstance(e, Fp8Expert):
+                self.local_experts[i] = Fp8Expert.from_expert(e)
+        self._moe_table = None
+        return self
+
+    def _table(self):
+        """The cached K.MoeTable of the local experts, rebuilt when a
+        weight or scale has moved (a host-side comparison of
+        data_ptr()s)."""
+        ex = self.local_experts
+        if self.quantized:
+            ws = [[getattr(e, n + "_w8") for e in ex]
+                  for n in Fp8Expert.NAMES]
+            scales = [[getattr(e, n + "_scale") for e in ex]
+                      for n in Fp8Expert.NAMES]
+        else:
+            ws = [[getattr(e, n).weight for e in ex]
+                  for n in Fp8Expert.NAMES]
+            scales = None
+        table = getattr(self, "_moe_table", None)
+        if table is None or \
+                table.ptrs != K.MoeTable.addresses(*ws, scales=scales):
+            table = self._moe_table = K.MoeTable(*ws, scales=scales)
+        return table
 
     def _wants_grad(self, x):
         return torch.is_grad_enabled() and (
@@ -293,17 +386,13 @@ class MoELayer(nn.Module):
         cfg.fused_moe_prefill whichever the batch size calls for. Reads
         nothing back, unlike forward's per-expert counts. The table of
         weight addresses is cached and rebuilt when a weight has moved (a
-        host-side comparison of data_ptr()s)."""
+        host-side comparison of data_ptr()s); after quantize_experts_ it
+        is the E4M3 table and the call takes the E4M3 kernels."""
         assert self.ep_world == 1, "fused MoE decode has no EP path"
         B, S, h = x.shape
         flat = x.reshape(B * S, h)
         logits = self.router(flat).float()
-        ws = ([e.gate_proj.weight for e in self.local_experts],
-              [e.up_proj.weight for e in self.local_experts],
-              [e.down_proj.weight for e in self.local_experts])
-        table = getattr(self, "_moe_table", None)
-        if table is None or table.ptrs != K.MoeTable.addresses(*ws):
-            table = self._moe_table = K.MoeTable(*ws)
+        table = self._table()
         if flat.size(0) * self.cfg.top_k > K.MOE_STREAM_MAX_ENTRIES:
             path = "tiled"
         out = K.moe_ffn(flat, logits, table, top_k=self.cfg.top_k,
@@ -396,6 +485,14 @@ class MixtralForCausalLM(nn.Module):
         for p in self.parameters():
             if p.dim() >= 2:
                 nn.init.normal_(p, mean=0.0, std=0.02)
+
+    def quantize_experts_(self):
+        """Weight-only FP8 for every layer's experts
+        (MoELayer.quantize_experts_); attention, router and lm_head stay
+        bf16. Inference-only from here on."""
+        for layer in self.layers:
+            layer.moe.quantize_experts_()
+        return self
 
     def forward(self, tokens, targets=None, cache=None):
         S = tokens.size(1)

@@ -990,9 +990,12 @@ void moe_combine(const torch::Tensor& y, const MoeRoute& r,
 // inter], bf16, 16-byte aligned) -> out [T, hidden] bf16.
 // tiled = false: the weight-stream kernels of moe.hip (decode); tiled =
 // true: wide route and the tiled GEMMs of moe_prefill.hip (splits unused).
+// e4m3 = true: the weights are E4M3 bytes of the same shapes and tab is
+// [6, E], rows 3 .. 5 the addresses of the gate / up / down row scales
+// (fp32 [inter] x2, [hidden], 16-byte aligned); the moe8 / moep8 kernels.
 torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
                       torch::Tensor tab, int64_t k, int64_t inter,
-                      int64_t splits, bool tiled) {
+                      int64_t splits, bool tiled, bool e4m3) {
   check_bf16(x, "x");
   TORCH_CHECK(x.dim() == 2 && logits.dim() == 2 &&
               logits.size(0) == x.size(0),
@@ -1003,9 +1006,10 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
               "moe_ffn needs hidden and inter to be multiples of 128, got ",
               hidden, " and ", inter);
   TORCH_CHECK(tab.is_cuda() && tab.scalar_type() == torch::kInt64 &&
-              tab.dim() == 2 && tab.size(0) == 3 && tab.size(1) == E &&
-              tab.is_contiguous(),
-              "tab must be a contiguous int64 [3, E] table on GPU");
+              tab.dim() == 2 && tab.size(0) == (e4m3 ? 6 : 3) &&
+              tab.size(1) == E && tab.is_contiguous(),
+              "tab must be a contiguous int64 [3, E] table on GPU ([6, E] "
+              "for E4M3 weights)");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
               "x must be 16-byte aligned");
   const MoeRoute r = moe_route_impl(logits, k, tiled);
@@ -1019,13 +1023,13 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
     const int2* tm = reinterpret_cast<const int2*>(r.tiles.data_ptr<int>());
     auto y = torch::empty({entries, hidden},
                           x.options().dtype(torch::kFloat32));
-    moep_gateup_kernel<<<dim3(tiles, inter / MOEP_TN), MOEP_BLOCK, 0,
-                         cur_stream()>>>(
+    const auto gateup = e4m3 ? moep8_gateup_kernel : moep_gateup_kernel;
+    const auto dn = e4m3 ? moep8_dn_kernel : moep_dn_kernel;
+    gateup<<<dim3(tiles, inter / MOEP_TN), MOEP_BLOCK, 0, cur_stream()>>>(
         bf(x), tp, r.order.data_ptr<int>(), r.offset.data_ptr<int>(), tm,
         bfm(h), (int)E, (int)k, (int)hidden, (int)inter);
     HIP_CHECK_KERNEL();
-    moep_dn_kernel<<<dim3(tiles, hidden / MOEP_TN), MOEP_BLOCK, 0,
-                     cur_stream()>>>(
+    dn<<<dim3(tiles, hidden / MOEP_TN), MOEP_BLOCK, 0, cur_stream()>>>(
         bf(h), tp, r.offset.data_ptr<int>(), tm, y.data_ptr<float>(),
         (int)E, (int)hidden, (int)inter);
     HIP_CHECK_KERNEL();
@@ -1038,13 +1042,13 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
               "down_splits must be at most inter / 128 and 64");
   auto y = torch::empty({splits, entries, hidden},
                         x.options().dtype(torch::kFloat32));
-  moe_gate_up_kernel<<<dim3(inter / MOE_ROWS, E), MOE_BLOCK, 0,
-                       cur_stream()>>>(
+  const auto gate_up = e4m3 ? moe8_gate_up_kernel : moe_gate_up_kernel;
+  const auto down = e4m3 ? moe8_down_kernel : moe_down_kernel;
+  gate_up<<<dim3(inter / MOE_ROWS, E), MOE_BLOCK, 0, cur_stream()>>>(
       bf(x), tp, r.order.data_ptr<int>(), r.offset.data_ptr<int>(), bfm(h),
       (int)E, (int)k, (int)hidden, (int)inter);
   HIP_CHECK_KERNEL();
-  moe_down_kernel<<<dim3(hidden / MOE_ROWS, E, splits), MOE_BLOCK, 0,
-                    cur_stream()>>>(
+  down<<<dim3(hidden / MOE_ROWS, E, splits), MOE_BLOCK, 0, cur_stream()>>>(
       bf(h), tp, r.offset.data_ptr<int>(), y.data_ptr<float>(), (int)E,
       (int)entries, (int)hidden, (int)inter);
   HIP_CHECK_KERNEL();
@@ -1162,7 +1166,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_ffn", &moe_ffn,
         "MoE feed-forward: x [T,hidden], logits fp32 [T,E], int64 [3,E] "
         "weight address table, top_k, inter, down splits (<= 0 = from "
-        "shapes), tiled (the prefill kernels) -> [T,hidden]");
+        "shapes), tiled (the prefill kernels), e4m3 (E4M3 weights, table "
+        "[6,E] with the row-scale addresses) -> [T,hidden]");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");

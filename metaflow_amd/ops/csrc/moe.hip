@@ -7,6 +7,7 @@
 //                       (order, offset) and each entry's slot in that order
 //   moe_gate_up_kernel  h[slot] = silu(x_t Wgate^T) * (x_t Wup^T)   bf16
 //   moe_down_kernel     y[split, slot] = h[slot, kpart] Wdown[:, kpart]^T
+//   moe8_gate_up_kernel, moe8_down_kernel   the same over E4M3 weights
 //   moe_combine_kernel  out[t] = sum_j weight[t, j] * sum_split y[.., slot]
 //
 // The two GEMM kernels are weight streams: at decode an expert sees a few
@@ -47,6 +48,22 @@
 // for n_e <= 32 (the decode case). Lanes past the last entry of a group
 // read a clamped row and store nothing. A block whose expert received no
 // entry exits at once (block-uniform test of offset[e + 1] == offset[e]).
+//
+// E4M3 weights (W8A16). moe8_gate_up_kernel / moe8_down_kernel are the same
+// bodies over one-byte weights: w[r, :] = e4m3(byte[r, :]) * scale[r], one
+// fp32 scale per weight row. A 128-element chunk of a row is then ONE
+// 128-byte line: lane (row l32, half-wave hi) reads the 64 contiguous bytes
+// at k = 64hi .. +63 of its row as four 16-byte loads, the two half-waves
+// again a whole line. Load j holds fragments f = 2j and 2j + 1: fragment f
+// is k = 64hi + 8f .. +7, and its B fragment is 16-byte piece 8hi + f of the
+// token's chunk row (the same LDS image, another walk through it). A chunk
+// is 4 loads and 16 raw registers per matrix, half of bf16. The bytes are
+// converted in registers right before their MFMA: v_cvt_pk_f32_fp8 on each
+// half word and one pack per pair (exact: every E4M3 value is a bf16
+// value), 8 VALU per fragment. The scales never touch the operands: a lane
+// holds 16 weight rows in the C layout (c_row), so it loads their 16 scales
+// per matrix once per block and multiplies the fp32 accumulators, gate and
+// up each by their own before SwiGLU, down before the partial is stored.
 //
 // Builds on attention.hip's helpers (mfma32, f16f, wave_coord, c_row,
 // pack_bf2) and is included after it, like append.hip.
@@ -158,20 +175,51 @@ moe_route_kernel(const float* __restrict__ logits, int T, int E, int k,
 // a generic pointer and flat loads (counted against the LDS counter too):
 // read them through a global-address-space pointer.
 typedef const __attribute__((address_space(1))) bf16x8* moe_gvec;
+typedef const __attribute__((address_space(1))) f32x4* moe_gf4;
+
+// The weight element: short = bf16, moe_e4m3 = one OCP E4M3 byte. A chunk
+// of a row is MoeW<W>::NV 16-byte loads per lane.
+typedef unsigned char moe_e4m3;
+template <typename W>
+struct MoeW {
+  static constexpr bool is8 = sizeof(W) == 1;
+  static constexpr int NV = is8 ? 4 : 8;
+};
+
+// half (0 / 1) of a 16-byte load of E4M3 -> one MFMA fragment, k ascending
+DEV bf16x8 moe8_frag(bf16x8 raw, int half) {
+  union {
+    bf16x8 v;
+    unsigned int w[4];
+  } r, o;
+  r.v = raw;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int w = (int)r.w[2 * half + i];
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8(w, false);
+    const auto b = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+    o.w[2 * i] = pack_bf2(a[0], a[1]);
+    o.w[2 * i + 1] = pack_bf2(b[0], b[1]);
+  }
+  return o.v;
+}
 
 // The lane addressing of one block's stream, fixed for the kernel's life.
 struct MoeLane {
-  int wcol;      // the lane's 64 contiguous bytes of half g: + 64 g + wcol
+  int wcol;      // the lane's 64 contiguous bytes: + 64 g + wcol (bf16,
+                 // half g, elements) or + wcol (E4M3, bytes)
   int xcol;      // staging: slot tid is piece tid % 16 of row tid / 16
   int st0, st1;  // its image offset, and that of row + 16
   int hi, key;   // fragment read: piece (8g + 4hi + j) ^ key of row l32
+                 // (E4M3: piece (8hi + f) ^ key)
   const char* xrow;
 };
 
+template <typename W>
 DEV MoeLane moe_lane(const char* lds) {
   const WaveCoord c = wave_coord();
   MoeLane L;
-  L.wcol = 32 * c.hi;
+  L.wcol = (MoeW<W>::is8 ? 64 : 32) * c.hi;
   L.xcol = 8 * lds_img::stage16_ch(threadIdx.x);
   L.st0 = lds_img::off_b(lds_img::stage16_row(threadIdx.x),
                          lds_img::stage16_ch(threadIdx.x));
@@ -183,15 +231,20 @@ DEV MoeLane moe_lane(const char* lds) {
   return L;
 }
 
-template <int NMAT>
-DEV void moe_load_w(bf16x8 (&w)[NMAT][8], const short* const (&wrow)[NMAT],
-                    long long k0, const MoeLane& L) {
+template <int NMAT, typename W>
+DEV void moe_load_w(bf16x8 (&w)[NMAT][MoeW<W>::NV],
+                    const W* const (&wrow)[NMAT], long long k0,
+                    const MoeLane& L) {
 #pragma unroll
   for (int m = 0; m < NMAT; ++m)
 #pragma unroll
-    for (int f = 0; f < 8; ++f)
-      w[m][f] = *(moe_gvec)(wrow[m] + k0 + 64 * (f >> 2) + L.wcol +
-                            8 * (f & 3));
+    for (int f = 0; f < MoeW<W>::NV; ++f) {
+      if constexpr (MoeW<W>::is8)
+        w[m][f] = *(moe_gvec)(wrow[m] + k0 + L.wcol + 16 * f);
+      else
+        w[m][f] = *(moe_gvec)(wrow[m] + k0 + 64 * (f >> 2) + L.wcol +
+                              8 * (f & 3));
+    }
 }
 
 // One chunk: issue the loads of chunk `nxt` (weights into wn, the two x
@@ -200,9 +253,10 @@ DEV void moe_load_w(bf16x8 (&w)[NMAT][8], const short* const (&wrow)[NMAT],
 // keeps the loads in front of the MFMAs: left alone, the compiler sinks
 // them to the end of the chunk, reloads wc in place and waits for them at
 // once, which leaves no load in flight while a wave computes.
-template <int NMAT>
-DEV void moe_chunk(const bf16x8 (&wc)[NMAT][8], bf16x8 (&wn)[NMAT][8],
-                   const short* const (&wrow)[NMAT], const short* xr0,
+template <int NMAT, typename W>
+DEV void moe_chunk(const bf16x8 (&wc)[NMAT][MoeW<W>::NV],
+                   bf16x8 (&wn)[NMAT][MoeW<W>::NV],
+                   const W* const (&wrow)[NMAT], const short* xr0,
                    const short* xr1, int nxt, int buf, char* lds,
                    const MoeLane& L, f16f (&acc)[NMAT]) {
   const long long kn = (long long)nxt * MOE_KC;
@@ -210,16 +264,22 @@ DEV void moe_chunk(const bf16x8 (&wc)[NMAT][8], bf16x8 (&wn)[NMAT][8],
   // chunk must not have to wait for the weights behind it
   const bf16x8 x0 = *(const bf16x8*)(xr0 + kn + L.xcol);
   const bf16x8 x1 = *(const bf16x8*)(xr1 + kn + L.xcol);
-  moe_load_w<NMAT>(wn, wrow, kn, L);
+  moe_load_w<NMAT, W>(wn, wrow, kn, L);
   __builtin_amdgcn_sched_barrier(0);
 
   const char* xb = L.xrow + buf * MOE_XBYTES;
 #pragma unroll
   for (int f = 0; f < 8; ++f) {
-    const int piece = 8 * (f >> 2) + 4 * L.hi + (f & 3);
+    const int piece = MoeW<W>::is8 ? 8 * L.hi + f
+                                   : 8 * (f >> 2) + 4 * L.hi + (f & 3);
     const bf16x8 b = *(const bf16x8*)(xb + 16 * (piece ^ L.key));
 #pragma unroll
-    for (int m = 0; m < NMAT; ++m) acc[m] = mfma32(wc[m][f], b, acc[m]);
+    for (int m = 0; m < NMAT; ++m) {
+      if constexpr (MoeW<W>::is8)
+        acc[m] = mfma32(moe8_frag(wc[m][f >> 1], f & 1), b, acc[m]);
+      else
+        acc[m] = mfma32(wc[m][f], b, acc[m]);
+    }
   }
   char* nb = lds + (buf ^ 1) * MOE_XBYTES;
   *(bf16x8*)(nb + L.st0) = x0;
@@ -235,13 +295,13 @@ DEV void moe_chunk(const bf16x8 (&wc)[NMAT][8], bf16x8 (&wn)[NMAT][8],
 // (the loop is unrolled by two), so no fragment is ever copied. The last
 // chunk "prefetches" itself rather than branch: served from cache, never
 // out of range.
-template <int NMAT>
-DEV void moe_stream(const short* const (&wrow)[NMAT], const short* xr0,
+template <int NMAT, typename W>
+DEV void moe_stream(const W* const (&wrow)[NMAT], const short* xr0,
                     const short* xr1, int c0, int c1, char* lds,
                     const MoeLane& L, f16f (&acc)[NMAT]) {
   if (c0 >= c1) return;
-  bf16x8 wa[NMAT][8], wb[NMAT][8];
-  moe_load_w<NMAT>(wa, wrow, (long long)c0 * MOE_KC, L);
+  bf16x8 wa[NMAT][MoeW<W>::NV], wb[NMAT][MoeW<W>::NV];
+  moe_load_w<NMAT, W>(wa, wrow, (long long)c0 * MOE_KC, L);
   {
     const bf16x8 x0 =
         *(const bf16x8*)(xr0 + (long long)c0 * MOE_KC + L.xcol);
@@ -252,11 +312,11 @@ DEV void moe_stream(const short* const (&wrow)[NMAT], const short* xr0,
   }
   __syncthreads();
   for (int ch = c0; ch < c1; ch += 2) {
-    moe_chunk<NMAT>(wa, wb, wrow, xr0, xr1, min(ch + 1, c1 - 1), 0, lds, L,
-                    acc);
+    moe_chunk<NMAT, W>(wa, wb, wrow, xr0, xr1, min(ch + 1, c1 - 1), 0, lds,
+                       L, acc);
     if (ch + 1 < c1)
-      moe_chunk<NMAT>(wb, wa, wrow, xr0, xr1, min(ch + 2, c1 - 1), 1, lds,
-                      L, acc);
+      moe_chunk<NMAT, W>(wb, wa, wrow, xr0, xr1, min(ch + 2, c1 - 1), 1, lds,
+                         L, acc);
   }
 }
 
@@ -267,34 +327,49 @@ DEV f16f moe_zero() {
   return z;
 }
 
+// The 16 scales of a lane's C rows (E4M3): rows base + c_row(r, hi) of the
+// fp32 [out] vector at address `addr`, as s[r / 4][r % 4].
+DEV void moe_scales(long long addr, int base, int hi, f32x4 (&s)[4]) {
+  const float* p = reinterpret_cast<const float*>(addr) + base;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s[q] = *(moe_gf4)(p + c_row(4 * q, hi));
+}
+
 // ---------------------------------------------------------------- gate/up
-// x [T, hidden] bf16; tab int64 [3, E] (gate, up, down weight addresses);
-// h [T*k, inter] bf16 in slot order. grid (inter / 128, E).
-MOE_KERNEL void __launch_bounds__(MOE_BLOCK)
-moe_gate_up_kernel(const short* __restrict__ x,
-                   const long long* __restrict__ tab,
-                   const int* __restrict__ order,
-                   const int* __restrict__ offset, short* __restrict__ h,
-                   int E, int k, int hidden, int inter) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * MOE_XBYTES];
+// x [T, hidden] bf16; tab int64 [3, E] (gate, up, down weight addresses),
+// for E4M3 [6, E]: then the gate, up, down scale addresses; h [T*k, inter]
+// bf16 in slot order. grid (inter / 128, E). One body for both weight
+// types under thin kernels.
+template <typename W>
+DEV void moe_gu_body(const short* __restrict__ x,
+                     const long long* __restrict__ tab,
+                     const int* __restrict__ order,
+                     const int* __restrict__ offset, short* __restrict__ h,
+                     int E, int k, int hidden, int inter, char* lds) {
   const int e = blockIdx.y;
   const int beg = offset[e], n_e = offset[e + 1] - beg;
   if (n_e == 0) return;
   const WaveCoord c = wave_coord();
-  const MoeLane L = moe_lane(lds);
+  const MoeLane L = moe_lane<W>(lds);
   const int row = blockIdx.x * MOE_ROWS + c.wid * 32 + c.l32;
-  const short* const wrow[2] = {
-      reinterpret_cast<const short*>(tab[e]) + (long long)row * hidden,
-      reinterpret_cast<const short*>(tab[E + e]) + (long long)row * hidden};
+  const W* const wrow[2] = {
+      reinterpret_cast<const W*>(tab[e]) + (long long)row * hidden,
+      reinterpret_cast<const W*>(tab[E + e]) + (long long)row * hidden};
   const int srow = threadIdx.x >> 4;
+  f32x4 sg[4], su[4];
+  if constexpr (MoeW<W>::is8) {
+    moe_scales(tab[3 * E + e], blockIdx.x * MOE_ROWS + c.wid * 32, c.hi, sg);
+    moe_scales(tab[4 * E + e], blockIdx.x * MOE_ROWS + c.wid * 32, c.hi, su);
+  }
 
   for (int g0 = 0; g0 < n_e; g0 += MOE_NTOK) {
     // the two rows this thread stages: token of entry order[..], clamped
     const int t0 = order[beg + min(g0 + srow, n_e - 1)] / k;
     const int t1 = order[beg + min(g0 + srow + 16, n_e - 1)] / k;
     f16f acc[2] = {moe_zero(), moe_zero()};
-    moe_stream<2>(wrow, x + (long long)t0 * hidden,
-                  x + (long long)t1 * hidden, 0, hidden / MOE_KC, lds, L, acc);
+    moe_stream<2, W>(wrow, x + (long long)t0 * hidden,
+                     x + (long long)t1 * hidden, 0, hidden / MOE_KC, lds, L,
+                     acc);
     if (g0 + c.l32 < n_e) {
       short* hp = h + (long long)(beg + g0 + c.l32) * inter +
                   blockIdx.x * MOE_ROWS + c.wid * 32;
@@ -303,8 +378,12 @@ moe_gate_up_kernel(const short* __restrict__ x,
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float gt = acc[0][4 * q + i];
-          v[i] = gt / (1.f + expf(-gt)) * acc[1][4 * q + i];
+          float gt = acc[0][4 * q + i], up = acc[1][4 * q + i];
+          if constexpr (MoeW<W>::is8) {
+            gt *= sg[q][i];
+            up *= su[q][i];
+          }
+          v[i] = gt / (1.f + expf(-gt)) * up;
         }
         uint2 pk;
         pk.x = pack_bf2(v[0], v[1]);
@@ -315,36 +394,57 @@ moe_gate_up_kernel(const short* __restrict__ x,
   }
 }
 
+MOE_KERNEL void __launch_bounds__(MOE_BLOCK)
+moe_gate_up_kernel(const short* __restrict__ x,
+                   const long long* __restrict__ tab,
+                   const int* __restrict__ order,
+                   const int* __restrict__ offset, short* __restrict__ h,
+                   int E, int k, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * MOE_XBYTES];
+  moe_gu_body<short>(x, tab, order, offset, h, E, k, hidden, inter, lds);
+}
+
+MOE_KERNEL void __launch_bounds__(MOE_BLOCK)
+moe8_gate_up_kernel(const short* __restrict__ x,
+                    const long long* __restrict__ tab,
+                    const int* __restrict__ order,
+                    const int* __restrict__ offset, short* __restrict__ h,
+                    int E, int k, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * MOE_XBYTES];
+  moe_gu_body<moe_e4m3>(x, tab, order, offset, h, E, k, hidden, inter, lds);
+}
+
 // ------------------------------------------------------------------- down
 // y [splits, T*k, hidden] fp32. grid (hidden / 128, E, splits); split s
 // takes chunks [s * NC / splits, (s + 1) * NC / splits) of inter.
-MOE_KERNEL void __launch_bounds__(MOE_BLOCK)
-moe_down_kernel(const short* __restrict__ h,
-                const long long* __restrict__ tab,
-                const int* __restrict__ offset, float* __restrict__ y,
-                int E, int entries, int hidden, int inter) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * MOE_XBYTES];
+template <typename W>
+DEV void moe_dn_body(const short* __restrict__ h,
+                     const long long* __restrict__ tab,
+                     const int* __restrict__ offset, float* __restrict__ y,
+                     int E, int entries, int hidden, int inter, char* lds) {
   const int e = blockIdx.y;
   const int beg = offset[e], n_e = offset[e + 1] - beg;
   if (n_e == 0) return;
   const WaveCoord c = wave_coord();
-  const MoeLane L = moe_lane(lds);
+  const MoeLane L = moe_lane<W>(lds);
   const int row = blockIdx.x * MOE_ROWS + c.wid * 32 + c.l32;
-  const short* const wrow[1] = {
-      reinterpret_cast<const short*>(tab[2 * E + e]) +
-      (long long)row * inter};
+  const W* const wrow[1] = {
+      reinterpret_cast<const W*>(tab[2 * E + e]) + (long long)row * inter};
   const int nc = inter / MOE_KC;
   const int c0 = (int)((long long)blockIdx.z * nc / gridDim.z);
   const int c1 = (int)((long long)(blockIdx.z + 1) * nc / gridDim.z);
   const int srow = threadIdx.x >> 4;
   float* ys = y + (long long)blockIdx.z * entries * hidden;
+  f32x4 sd[4];
+  if constexpr (MoeW<W>::is8)
+    moe_scales(tab[5 * E + e], blockIdx.x * MOE_ROWS + c.wid * 32, c.hi, sd);
 
   for (int g0 = 0; g0 < n_e; g0 += MOE_NTOK) {
     const int s0 = beg + min(g0 + srow, n_e - 1);
     const int s1 = beg + min(g0 + srow + 16, n_e - 1);
     f16f acc[1] = {moe_zero()};
-    moe_stream<1>(wrow, h + (long long)s0 * inter, h + (long long)s1 * inter,
-                  c0, c1, lds, L, acc);
+    moe_stream<1, W>(wrow, h + (long long)s0 * inter,
+                     h + (long long)s1 * inter, c0, c1, lds, L, acc);
     if (g0 + c.l32 < n_e) {
       float* yp = ys + (long long)(beg + g0 + c.l32) * hidden +
                   blockIdx.x * MOE_ROWS + c.wid * 32;
@@ -352,11 +452,32 @@ moe_down_kernel(const short* __restrict__ h,
       for (int q = 0; q < 4; ++q) {
         f32x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = acc[0][4 * q + i];
+        for (int i = 0; i < 4; ++i) {
+          v[i] = acc[0][4 * q + i];
+          if constexpr (MoeW<W>::is8) v[i] *= sd[q][i];
+        }
         *(f32x4*)(yp + c_row(4 * q, c.hi)) = v;
       }
     }
   }
+}
+
+MOE_KERNEL void __launch_bounds__(MOE_BLOCK)
+moe_down_kernel(const short* __restrict__ h,
+                const long long* __restrict__ tab,
+                const int* __restrict__ offset, float* __restrict__ y,
+                int E, int entries, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * MOE_XBYTES];
+  moe_dn_body<short>(h, tab, offset, y, E, entries, hidden, inter, lds);
+}
+
+MOE_KERNEL void __launch_bounds__(MOE_BLOCK)
+moe8_down_kernel(const short* __restrict__ h,
+                 const long long* __restrict__ tab,
+                 const int* __restrict__ offset, float* __restrict__ y,
+                 int E, int entries, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * MOE_XBYTES];
+  moe_dn_body<moe_e4m3>(h, tab, offset, y, E, entries, hidden, inter, lds);
 }
 
 // ---------------------------------------------------------------- combine

@@ -13,6 +13,7 @@
 //   moep_scatter_kernel  order / slot from offset + block base + rank
 //   moep_gateup_kernel   h[slot] = silu(x_t Wgate^T) * (x_t Wup^T)    bf16
 //   moep_dn_kernel       y[slot] = h[slot] Wdown^T                    fp32
+//   moep8_gateup_kernel, moep8_dn_kernel   the same over E4M3 weights
 //   (moe.hip's combine kernel, with one split, ends the block)
 //
 // Tile map. An M tile is MOEP_TM consecutive slots of one expert. Their
@@ -51,7 +52,21 @@
 // depend on where the routing puts it. Entry rows past the end of the
 // expert's run load a clamped row (inside x or h) and store nothing.
 //
-// Included after moe.hip (MOE_KERNEL, moe_gvec, moe_zero, the limits).
+// E4M3 weights (moe.hip's format: bytes and one fp32 scale per weight row).
+// A weight row's chunk is 64 bytes, four 16-byte pieces: thread tid loads
+// piece tid % 4 of rows tid / 4 + 64 p, p = 0..1, of every weight image (two
+// loads where bf16 has four), converts the 16 bytes to bf16 in registers
+// after the chunk's MFMAs and writes them as pieces 2 (tid % 4) and + 1 of
+// the same image, so fragment reads and the MFMA loop are those of bf16.
+// That write: 16 consecutive lanes are 4 pieces of 4 consecutive rows, whose
+// keys are a, a, a + 1, a + 1 with a even: even (or odd) pieces XORed with
+// an even key stay even (odd), with an odd key turn odd (even), and the two
+// rows of a key differ in parity, so the 16 lanes again meet each 16-byte
+// bank group once. The scales multiply the fp32 accumulators in the
+// epilogue, four f32x4 loads per 32 weight rows in C-register order.
+//
+// Included after moe.hip (MOE_KERNEL, moe_gvec, moe_zero, MoeW, moe8_frag,
+// moe_scales, the limits).
 
 #define MOEP_TM 128   // entries per M tile
 #define MOEP_TN 128   // weight rows per block
@@ -194,15 +209,19 @@ DEV constexpr int moep_off(int row, int ch) {
 // offsets are st + 4096 p.
 struct MoepLane {
   int st;      // moep_off(tid / 8, tid % 8)
+  int stw;     // weight images: st, or for E4M3 moep_off(tid / 4, 2 (tid % 4))
   int fo[4];   // fragment read, k-step s: piece (2 s + hi) ^ key of row l32
   int arow;    // byte offset of the wave's first weight row + l32
   int brow;    // and of its first entry row + l32
 };
 
+template <typename W>
 DEV MoepLane moep_lane() {
   const WaveCoord c = wave_coord();
   MoepLane L;
   L.st = moep_off(threadIdx.x >> 3, threadIdx.x & 7);
+  L.stw = MoeW<W>::is8 ? moep_off(threadIdx.x >> 2, 2 * (threadIdx.x & 3))
+                       : L.st;
   const int key = (c.l32 >> 1) & 7;
 #pragma unroll
   for (int s = 0; s < 4; ++s) L.fo[s] = 16 * ((2 * s + c.hi) ^ key);
@@ -215,16 +234,18 @@ DEV MoepLane moep_lane() {
 // over nc chunks of K, for NMAT weight matrices that share rows and X.
 // er[p]: the entry row (already clamped) this thread stages as row tid / 8
 // + 32 p of the tile, at its piece; wr[m]: row tid / 8 of the block's
-// weight rows at its piece, the rows + 32 p being wstep elements on. The
+// weight rows at its piece, the rows + 32 p being wstep elements on (E4M3:
+// row tid / 4 at its 16-byte piece, the row + 64 being wstep bytes on). The
 // last chunk "prefetches" itself rather than branch: served from cache,
 // never out of range.
-template <int NMAT>
+template <int NMAT, typename W>
 DEV void moep_tile(const short* const (&er)[4],
-                   const short* const (&wr)[NMAT], long long wstep, int nc,
+                   const W* const (&wr)[NMAT], long long wstep, int nc,
                    char* lds, const MoepLane& L,
                    f16f (&acc)[NMAT][2][2]) {
   constexpr int BUF = (1 + NMAT) * MOEP_IMG;
-  bf16x8 se[4], sw[NMAT][4];
+  constexpr int NW = MoeW<W>::is8 ? 2 : 4;  // weight loads per image
+  bf16x8 se[4], sw[NMAT][NW];
 
   auto load = [&](int ch) {
     const long long k0 = (long long)ch * MOEP_KC;
@@ -233,7 +254,7 @@ DEV void moep_tile(const short* const (&er)[4],
 #pragma unroll
     for (int m = 0; m < NMAT; ++m)
 #pragma unroll
-      for (int p = 0; p < 4; ++p)
+      for (int p = 0; p < NW; ++p)
         sw[m][p] = *(moe_gvec)(wr[m] + p * wstep + k0);
   };
   auto publish = [&](int buf) {
@@ -243,8 +264,16 @@ DEV void moep_tile(const short* const (&er)[4],
 #pragma unroll
     for (int m = 0; m < NMAT; ++m)
 #pragma unroll
-      for (int p = 0; p < 4; ++p)
-        *(bf16x8*)(b + (1 + m) * MOEP_IMG + 4096 * p) = sw[m][p];
+      for (int p = 0; p < NW; ++p) {
+        if constexpr (MoeW<W>::is8) {
+          // pieces 2c and 2c + 1 of one row sit 16 bytes apart either way
+          char* w = lds + buf * BUF + (1 + m) * MOEP_IMG + 8192 * p;
+          *(bf16x8*)(w + L.stw) = moe8_frag(sw[m][p], 0);
+          *(bf16x8*)(w + (L.stw ^ 16)) = moe8_frag(sw[m][p], 1);
+        } else {
+          *(bf16x8*)(b + (1 + m) * MOEP_IMG + 4096 * p) = sw[m][p];
+        }
+      }
   };
 
   load(0);
@@ -279,22 +308,24 @@ DEV void moep_tile(const short* const (&er)[4],
 }
 
 // ---------------------------------------------------------------- gate/up
-// x [T, hidden] bf16; tab int64 [3, E]; h [T*k, inter] bf16 in slot order.
-// grid (max_tiles, inter / 128): the M tiles of one weight tile run side
-// by side, so an expert's weight rows are shared in L2 by its tiles.
-MOE_KERNEL void __launch_bounds__(MOEP_BLOCK)
-moep_gateup_kernel(const short* __restrict__ x,
-                   const long long* __restrict__ tab,
-                   const int* __restrict__ order,
-                   const int* __restrict__ offset,
-                   const int2* __restrict__ tiles, short* __restrict__ h,
-                   int E, int k, int hidden, int inter) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * 3 * MOEP_IMG];
+// x [T, hidden] bf16; tab int64 [3, E] (E4M3: [6, E], the scale addresses
+// behind the weights'); h [T*k, inter] bf16 in slot order. grid (max_tiles,
+// inter / 128): the M tiles of one weight tile run side by side, so an
+// expert's weight rows are shared in L2 by its tiles. One body for both
+// weight types under thin kernels.
+template <typename W>
+DEV void moep_gu_body(const short* __restrict__ x,
+                      const long long* __restrict__ tab,
+                      const int* __restrict__ order,
+                      const int* __restrict__ offset,
+                      const int2* __restrict__ tiles, short* __restrict__ h,
+                      int E, int k, int hidden, int inter, char* lds) {
+  constexpr bool is8 = MoeW<W>::is8;
   const int2 tl = tiles[blockIdx.x];
   if (tl.x < 0) return;
   const int e = tl.x, slot0 = tl.y, end = offset[e + 1];
   const WaveCoord c = wave_coord();
-  const MoepLane L = moep_lane();
+  const MoepLane L = moep_lane<W>();
   const int srow = threadIdx.x >> 3, scol = 8 * (threadIdx.x & 7);
   const int n0 = blockIdx.y * MOEP_TN;
 
@@ -304,10 +335,12 @@ moep_gateup_kernel(const short* __restrict__ x,
     const int t = order[min(slot0 + srow + 32 * p, end - 1)] / k;
     er[p] = x + (long long)t * hidden + scol;
   }
-  const long long w0 = (long long)(n0 + srow) * hidden + scol;
-  const short* const wr[2] = {
-      reinterpret_cast<const short*>(tab[e]) + w0,
-      reinterpret_cast<const short*>(tab[E + e]) + w0};
+  const long long w0 =
+      is8 ? (long long)(n0 + (threadIdx.x >> 2)) * hidden +
+                16 * (threadIdx.x & 3)
+          : (long long)(n0 + srow) * hidden + scol;
+  const W* const wr[2] = {reinterpret_cast<const W*>(tab[e]) + w0,
+                          reinterpret_cast<const W*>(tab[E + e]) + w0};
 
   f16f acc[2][2][2];
 #pragma unroll
@@ -316,8 +349,18 @@ moep_gateup_kernel(const short* __restrict__ x,
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[m][i][j] = moe_zero();
-  moep_tile<2>(er, wr, 32ll * hidden, hidden / MOEP_KC, lds, L, acc);
+  moep_tile<2, W>(er, wr, (is8 ? 64ll : 32ll) * hidden, hidden / MOEP_KC,
+                  lds, L, acc);
 
+  f32x4 sg[2][4], su[2][4];
+  if constexpr (is8) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int r0 = n0 + 64 * (c.wid >> 1) + 32 * i;
+      moe_scales(tab[3 * E + e], r0, c.hi, sg[i]);
+      moe_scales(tab[4 * E + e], r0, c.hi, su[i]);
+    }
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int s = slot0 + 64 * (c.wid & 1) + 32 * j + c.l32;
@@ -331,8 +374,12 @@ moep_gateup_kernel(const short* __restrict__ x,
           float v[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float gt = acc[0][i][j][4 * q + r];
-            v[r] = gt / (1.f + expf(-gt)) * acc[1][i][j][4 * q + r];
+            float gt = acc[0][i][j][4 * q + r], up = acc[1][i][j][4 * q + r];
+            if constexpr (is8) {
+              gt *= sg[i][q][r];
+              up *= su[i][q][r];
+            }
+            v[r] = gt / (1.f + expf(-gt)) * up;
           }
           uint2 pk;
           pk.x = pack_bf2(v[0], v[1]);
@@ -344,21 +391,45 @@ moep_gateup_kernel(const short* __restrict__ x,
   }
 }
 
+MOE_KERNEL void __launch_bounds__(MOEP_BLOCK)
+moep_gateup_kernel(const short* __restrict__ x,
+                   const long long* __restrict__ tab,
+                   const int* __restrict__ order,
+                   const int* __restrict__ offset,
+                   const int2* __restrict__ tiles, short* __restrict__ h,
+                   int E, int k, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * 3 * MOEP_IMG];
+  moep_gu_body<short>(x, tab, order, offset, tiles, h, E, k, hidden, inter,
+                      lds);
+}
+
+MOE_KERNEL void __launch_bounds__(MOEP_BLOCK)
+moep8_gateup_kernel(const short* __restrict__ x,
+                    const long long* __restrict__ tab,
+                    const int* __restrict__ order,
+                    const int* __restrict__ offset,
+                    const int2* __restrict__ tiles, short* __restrict__ h,
+                    int E, int k, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * 3 * MOEP_IMG];
+  moep_gu_body<moe_e4m3>(x, tab, order, offset, tiles, h, E, k, hidden,
+                         inter, lds);
+}
+
 // ------------------------------------------------------------------- down
 // y [T*k, hidden] fp32 in slot order. grid (max_tiles, hidden / 128). The
 // whole of inter is summed in one block: no split of K.
-MOE_KERNEL void __launch_bounds__(MOEP_BLOCK)
-moep_dn_kernel(const short* __restrict__ h,
-               const long long* __restrict__ tab,
-               const int* __restrict__ offset,
-               const int2* __restrict__ tiles, float* __restrict__ y,
-               int E, int hidden, int inter) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * 2 * MOEP_IMG];
+template <typename W>
+DEV void moep_dn_body(const short* __restrict__ h,
+                      const long long* __restrict__ tab,
+                      const int* __restrict__ offset,
+                      const int2* __restrict__ tiles, float* __restrict__ y,
+                      int E, int hidden, int inter, char* lds) {
+  constexpr bool is8 = MoeW<W>::is8;
   const int2 tl = tiles[blockIdx.x];
   if (tl.x < 0) return;
   const int e = tl.x, slot0 = tl.y, end = offset[e + 1];
   const WaveCoord c = wave_coord();
-  const MoepLane L = moep_lane();
+  const MoepLane L = moep_lane<W>();
   const int srow = threadIdx.x >> 3, scol = 8 * (threadIdx.x & 7);
   const int n0 = blockIdx.y * MOEP_TN;
 
@@ -367,17 +438,27 @@ moep_dn_kernel(const short* __restrict__ h,
   for (int p = 0; p < 4; ++p)
     er[p] = h + (long long)min(slot0 + srow + 32 * p, end - 1) * inter +
             scol;
-  const short* const wr[1] = {
-      reinterpret_cast<const short*>(tab[2 * E + e]) +
-      (long long)(n0 + srow) * inter + scol};
+  const long long w0 =
+      is8 ? (long long)(n0 + (threadIdx.x >> 2)) * inter +
+                16 * (threadIdx.x & 3)
+          : (long long)(n0 + srow) * inter + scol;
+  const W* const wr[1] = {reinterpret_cast<const W*>(tab[2 * E + e]) + w0};
 
   f16f acc[1][2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[0][i][j] = moe_zero();
-  moep_tile<1>(er, wr, 32ll * inter, inter / MOEP_KC, lds, L, acc);
+  moep_tile<1, W>(er, wr, (is8 ? 64ll : 32ll) * inter, inter / MOEP_KC, lds,
+                  L, acc);
 
+  f32x4 sd[2][4];
+  if constexpr (is8) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      moe_scales(tab[5 * E + e], n0 + 64 * (c.wid >> 1) + 32 * i, c.hi,
+                 sd[i]);
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int s = slot0 + 64 * (c.wid & 1) + 32 * j + c.l32;
@@ -390,10 +471,33 @@ moep_dn_kernel(const short* __restrict__ h,
         for (int q = 0; q < 4; ++q) {
           f32x4 v;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = acc[0][i][j][4 * q + r];
+          for (int r = 0; r < 4; ++r) {
+            v[r] = acc[0][i][j][4 * q + r];
+            if constexpr (is8) v[r] *= sd[i][q][r];
+          }
           *(f32x4*)(yp + c_row(4 * q, c.hi)) = v;
         }
       }
     }
   }
+}
+
+MOE_KERNEL void __launch_bounds__(MOEP_BLOCK)
+moep_dn_kernel(const short* __restrict__ h,
+               const long long* __restrict__ tab,
+               const int* __restrict__ offset,
+               const int2* __restrict__ tiles, float* __restrict__ y,
+               int E, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * 2 * MOEP_IMG];
+  moep_dn_body<short>(h, tab, offset, tiles, y, E, hidden, inter, lds);
+}
+
+MOE_KERNEL void __launch_bounds__(MOEP_BLOCK)
+moep8_dn_kernel(const short* __restrict__ h,
+                const long long* __restrict__ tab,
+                const int* __restrict__ offset,
+                const int2* __restrict__ tiles, float* __restrict__ y,
+                int E, int hidden, int inter) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * 2 * MOEP_IMG];
+  moep_dn_body<moe_e4m3>(h, tab, offset, tiles, y, E, hidden, inter, lds);
 }

@@ -1046,17 +1046,56 @@ def moe_route(logits, top_k, wide=None):
                                      top_k, bool(wide))[:4])
 
 
+def moe_quant_weight(w):
+    """Quantise an expert weight [out, in] to E4M3 with one fp32 scale per
+    output row, the convention of kv_quant_ref with a row in place of a
+    (page, head): scale[r] = amax|w[r, :]| / 448 (1.0 for an all-zero row),
+    byte = RNE-E4M3 of clamp(w / scale, -448, 448). Returns (w8
+    float8_e4m3fn [out, in], scale fp32 [out]). A one-time torch
+    composition for any device, on no hot path."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=-1)
+    scale = torch.where(amax > 0, amax / E4M3_MAX, torch.ones_like(amax))
+    y = (wf / scale.unsqueeze(-1)).clamp(-E4M3_MAX, E4M3_MAX)
+    return y.to(torch.float8_e4m3fn).contiguous(), scale.contiguous()
+
+
+def moe_dequant_ref(w8, scale, dtype=torch.float32):
+    """w[r, :] = e4m3(w8[r, :]) * scale[r], computed in fp32 (fp64 when
+    asked for fp64, where it is exact) and rounded once to ``dtype``."""
+    wide = torch.float64 if dtype == torch.float64 else torch.float32
+    return (w8.to(wide) * scale.to(wide).unsqueeze(-1)).to(dtype)
+
+
 class MoeTable(object):
     """The expert weights of one MoE layer as the kernels take them: an
     int64 [3, E] device table of the gate / up / down base addresses. The
     parameters stay where they are; ``ptrs`` is the host copy of the
-    addresses, to compare against when a weight may have moved."""
+    addresses, to compare against when a weight may have moved.
 
-    def __init__(self, w_gate, w_up, w_down):
+    The weights are either all bf16, or all float8_e4m3fn with ``scales =
+    (s_gate, s_up, s_down)``, sequences of E fp32 row-scale vectors of
+    length ``out`` (moe_quant_weight): the table is then [6, E], the scale
+    addresses behind the weights', and ``fp8`` is set."""
+
+    def __init__(self, w_gate, w_up, w_down, scales=None):
         self.weights = (tuple(w_gate), tuple(w_up), tuple(w_down))
         E = len(self.weights[0])
         if E == 0 or any(len(ws) != E for ws in self.weights):
             raise ValueError("moe_ffn needs E gate, up and down weights")
+        dtypes = set(w.dtype for ws in self.weights for w in ws)
+        if dtypes == {torch.float8_e4m3fn}:
+            self.fp8 = True
+        elif torch.float8_e4m3fn in dtypes:
+            raise ValueError("expert weights must be all bf16 or all "
+                             "float8_e4m3fn, not a mix")
+        else:
+            self.fp8 = False
+        if self.fp8 and scales is None:
+            raise ValueError("float8_e4m3fn expert weights need scales="
+                             "(s_gate, s_up, s_down)")
+        if not self.fp8 and scales is not None:
+            raise ValueError("scales go with float8_e4m3fn expert weights")
         self.inter, self.hidden = self.weights[0][0].shape
         if self.hidden % 128 or self.inter % 128:
             raise ValueError(
@@ -1065,6 +1104,7 @@ class MoeTable(object):
         shapes = ((self.inter, self.hidden),) * 2 + \
             ((self.hidden, self.inter),)
         dev = self.weights[0][0].device
+        wtype = torch.float8_e4m3fn if self.fp8 else torch.bfloat16
         for ws, shape in zip(self.weights, shapes):
             for w in ws:
                 if tuple(w.shape) != shape or w.device != dev:
@@ -1072,20 +1112,49 @@ class MoeTable(object):
                                      "and be [inter, hidden] (gate, up) and "
                                      "[hidden, inter] (down)")
                 if dev.type == "cuda" and not (
-                        w.dtype == torch.bfloat16 and w.is_contiguous()
+                        w.dtype == wtype and w.is_contiguous()
                         and w.data_ptr() % 16 == 0):
                     raise ValueError("expert weights must be contiguous "
-                                     "16-byte-aligned bf16 on the GPU")
-        self.ptrs = self.addresses(*self.weights)
+                                     "16-byte-aligned %s on the GPU"
+                                     % ("float8_e4m3fn" if self.fp8
+                                        else "bf16"))
+        self.scales = None
+        if self.fp8:
+            self.scales = tuple(tuple(ss) for ss in scales)
+            if len(self.scales) != 3 or any(len(ss) != E
+                                            for ss in self.scales):
+                raise ValueError("scales must be (s_gate, s_up, s_down), E "
+                                 "vectors each")
+            for ss, shape in zip(self.scales, shapes):
+                for sc in ss:
+                    if not (sc.dtype == torch.float32
+                            and tuple(sc.shape) == (shape[0],)
+                            and sc.device == dev and sc.is_contiguous()
+                            and sc.data_ptr() % 16 == 0):
+                        raise ValueError(
+                            "an expert weight's scales must be a contiguous "
+                            "16-byte-aligned fp32 vector of its out rows, on "
+                            "the weights' device")
+        self.ptrs = self.addresses(*self.weights, scales=self.scales)
         self.tab = None
         if dev.type == "cuda":
             self.tab = torch.tensor(self.ptrs, dtype=torch.int64,
-                                    device=dev).reshape(3, E)
+                                    device=dev).reshape(-1, E)
 
     @staticmethod
-    def addresses(w_gate, w_up, w_down):
-        return tuple(w.data_ptr() for ws in (w_gate, w_up, w_down)
-                     for w in ws)
+    def addresses(w_gate, w_up, w_down, scales=None):
+        return tuple(t.data_ptr()
+                     for ts in (w_gate, w_up, w_down) + tuple(scales or ())
+                     for t in ts)
+
+    def dequantized(self, dtype=torch.float32):
+        """(w_gate, w_up, w_down) as ``dtype`` tensors: the weights
+        themselves converted, or moe_dequant_ref of E4M3 ones."""
+        if not self.fp8:
+            return tuple([w.to(dtype) for w in ws] for ws in self.weights)
+        return tuple([moe_dequant_ref(w, sc, dtype)
+                      for w, sc in zip(ws, ss)]
+                     for ws, ss in zip(self.weights, self.scales))
 
 
 def moe_ffn_ref(x, logits, w_gate, w_up, w_down, top_k,
@@ -1112,8 +1181,11 @@ def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
     logits [T, E] -> [T, hidden] in x's dtype.
 
     w_gate, w_up, w_down: sequences of E weights ([inter, hidden] twice,
-    [hidden, inter]), or a prebuilt MoeTable as w_gate alone. hidden and
-    inter must be multiples of 128; E <= 64, top_k <= 8, T * top_k <= 65536.
+    [hidden, inter]), or a prebuilt MoeTable as w_gate alone; a table of
+    E4M3 weights and row scales (weight-only FP8: x, h, the partials and
+    the output keep their types) takes the E4M3 kernels of the same path.
+    hidden and inter must be multiples of 128; E <= 64, top_k <= 8, T *
+    top_k <= 65536.
     path: "stream" -> moe.hip, the decode kernels that stream an expert's
     weights once per 32 entries (T * top_k <= 2048); "tiled" ->
     moe_prefill.hip, the prefill kernels (multi-block route, 128 x 128
@@ -1124,7 +1196,8 @@ def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
 
     Either path: route, gate/up + SwiGLU, down, combine, with nothing read
     on the host and no atomics, so the call is deterministic and
-    hipGraph-capturable. CPU -> moe_ffn_ref. Inference-only."""
+    hipGraph-capturable. CPU -> moe_ffn_ref (on the dequantised weights of
+    an E4M3 table). Inference-only."""
     table = w_gate if isinstance(w_gate, MoeTable) else \
         MoeTable(w_gate, w_up, w_down)
     _moe_no_grad(x, logits, *[w for ws in table.weights for w in ws])
@@ -1144,13 +1217,14 @@ def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
     if path == "tiled" and down_splits is not None:
         raise ValueError("moe_ffn: down_splits applies to the stream path")
     if not x.is_cuda:
-        return moe_ffn_ref(x, logits, *table.weights, top_k).to(x.dtype)
+        ws = table.dequantized() if table.fp8 else table.weights
+        return moe_ffn_ref(x, logits, *ws, top_k).to(x.dtype)
     if down_splits is not None and not \
             1 <= down_splits <= min(table.inter // 128, 64):
         raise ValueError("down_splits must be in [1, min(inter / 128, 64)]")
     return hip_ext().moe_ffn(x.contiguous(), logits.float().contiguous(),
                              table.tab, top_k, table.inter,
-                             down_splits or 0, path == "tiled")
+                             down_splits or 0, path == "tiled", table.fp8)
 
 
 # ================================ adam =====================================
