@@ -2,7 +2,7 @@
 """Decode (serving) throughput: KV-cache generate() tokens/sec.
 
     python benchmarks/bench_decode.py [--model llama3-8b] [--batch 8]
-        [--prompt 512] [--new 128]
+        [--prompt 512] [--new 128] [--weights-fp8]
     python benchmarks/bench_decode.py --model mixtral-tiny --fused-moe
     python benchmarks/bench_decode.py --model mixtral-tiny \
         --fused-moe-prefill --prompt-range 1024 2047
@@ -10,6 +10,8 @@
 Measures prefill time and per-token decode rate separately. The decode
 attention runs the split-K flash-decode kernel (ops/csrc/decode.hip)
 straight over the cache allocation; prefill runs the flash fwd kernel.
+--weights-fp8 (llama3-8b) quantises the projections first
+(LlamaForCausalLM.quantize_weights_, ops/csrc/linear_fp8.hip).
 
 --fused-moe (mixtral-tiny) measures the serving decode step instead: the
 continuous batcher over --batch requests of --new tokens with the eager MoE
@@ -183,7 +185,13 @@ def main():
                    help="--fused-moe-prefill: the batcher's prefill_chunk "
                         "(the fused block serves up to 384 entries per "
                         "expert, 768 tokens of mixtral-tiny, per call)")
+    p.add_argument("--weights-fp8", action="store_true",
+                   help="llama3-8b: weight-only FP8 projections "
+                        "(LlamaForCausalLM.quantize_weights_)")
     args = p.parse_args()
+    if args.weights_fp8 and args.model != "llama3-8b":
+        p.error("--weights-fp8 needs --model llama3-8b (shapes that are "
+                "multiples of 128)")
     if (args.fused_moe or args.fused_moe_prefill) and \
             args.model != "mixtral-tiny":
         p.error("--fused-moe and --fused-moe-prefill need --model "
@@ -215,6 +223,8 @@ def main():
     with torch.device(device):
         model = cls(cfg)
     model.eval()
+    if args.weights_fp8:
+        model.quantize_weights_()
     tok = torch.randint(0, cfg.vocab_size, (args.batch, prompt_len),
                         device=device)
 
@@ -256,6 +266,7 @@ def main():
         "ms_per_decode_step": round(decode_s / args.new * 1000, 2),
         "config": {"model": args.model, "batch": args.batch,
                    "prompt": prompt_len, "new": args.new,
+                   "weights_fp8": args.weights_fp8,
                    "device": str(device)},
     }), flush=True)
 

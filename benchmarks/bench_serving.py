@@ -5,6 +5,7 @@ varlen flash-decode kernel), hipGraph replay vs eager decode.
     python benchmarks/bench_serving.py [--model llama3-8b] [--slots 8]
         [--requests 24] [--prompt 256] [--new 64] [--pages N [--kv-fp8]]
         [--temperature T] [--top-k K] [--top-p P] [--seed S]
+        [--weights-fp8 [--rounds 3]]
 
 --pages N serves the same request stream from a paged KV cache of N
 64-row pages (ContinuousBatcher(num_pages=N)) instead of dense slots;
@@ -13,6 +14,9 @@ varlen flash-decode kernel), hipGraph replay vs eager decode.
 --temperature > 0 samples every request (with the optional --top-k /
 --top-p cuts; request i is seeded --seed + i); the default decodes
 greedily.
+--weights-fp8 compares the bf16 model with a weight-only FP8 copy of it
+(E4M3 projections, ops/csrc/linear_fp8.hip) in one process, see
+weights_fp8().
 """
 
 import argparse
@@ -55,8 +59,55 @@ def run_one(model, graph, args, device):
     return n, dt, batcher._graph is not None
 
 
+def weights_fp8(model, args, device):
+    """The bf16 model and a copy with weight-only FP8 projections
+    (quantize_weights_) serve the same request stream in turns, graph
+    replay, --rounds rounds after a warm-up round of both; and the format's
+    cost: relative L2 of the quantised model's logits against the bf16
+    model's on one prompt of --prompt tokens."""
+    import copy
+
+    import torch
+
+    models = {"bf16": model,
+              "weights_fp8": copy.deepcopy(model).quantize_weights_()}
+    random.seed(1)
+    tokens = torch.tensor([[random.randrange(2, 1000)
+                            for _ in range(args.prompt)]], device=device)
+    with torch.no_grad():
+        ref = models["bf16"](tokens).float()
+        rel = float((models["weights_fp8"](tokens).float() - ref).norm()
+                    / ref.norm())
+    for m in models.values():
+        run_one(m, "auto", args, device)
+    runs = {n: [] for n in models}
+    for _ in range(args.rounds):
+        for name, m in models.items():
+            n, dt, used_graph = run_one(m, "auto", args, device)
+            assert used_graph
+            runs[name].append(round(n / dt, 1))
+    print(json.dumps({
+        "metric": "serving tokens/sec, bf16 vs weight-only FP8, graph replay",
+        "unit": "tokens/s", "higher_is_better": True, "runs": runs,
+        "every_fp8_run_above_every_bf16_run":
+            min(runs["weights_fp8"]) > max(runs["bf16"]),
+        "logits_rel_l2_vs_bf16": round(rel, 5),
+        "config": {"model": args.model, "slots": args.slots,
+                   "requests": args.requests, "prompt_max": args.prompt,
+                   "new": args.new, "prefill_chunk": args.prefill_chunk,
+                   "pages": args.pages, "kv_fp8": args.kv_fp8,
+                   "rounds": args.rounds},
+    }), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--weights-fp8", action="store_true",
+                   help="serve a copy with weight-only FP8 projections "
+                        "(LlamaForCausalLM.quantize_weights_) in turns with "
+                        "the bf16 model, graph replay, and report both")
+    p.add_argument("--rounds", type=int, default=3,
+                   help="with --weights-fp8: rounds after the warm-up round")
     p.add_argument("--model", default="llama3-8b",
                    choices=["llama3-8b", "tiny"])
     p.add_argument("--slots", type=int, default=8)
@@ -91,6 +142,9 @@ def main():
     with torch.device(device):
         model = LlamaForCausalLM(cfg).eval()
 
+    if args.weights_fp8:
+        weights_fp8(model, args, device)
+        return
     for graph in (False, "auto"):
         n, dt, used_graph = run_one(model, graph, args, device)
         print(json.dumps({

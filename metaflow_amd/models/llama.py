@@ -74,6 +74,59 @@ class Linear(nn.Module):
         return tuned_linear(x, self.weight)
 
 
+#: rows of x up to which a quantised projection takes the stream kernel:
+#: at 8B geometry it beat the dequantising fallback on all five projections
+#: at 64 and 128 rows (two passes over the weights); at 256 it lost on
+#: gate|up and on the four layer projections together (docs/KERNELS.md,
+#: "FP8 dense weights")
+STREAM_MAX_ROWS = 128
+
+
+class Fp8WeightLinear(nn.Module):
+    """A bias-free linear with weight-only FP8 weights: E4M3 bytes
+    ``weight8`` [out, in] and one fp32 ``scale`` per output row
+    (K.moe_quant_weight), held as buffers, so state_dict round-trips and
+    there is nothing to train. Up to STREAM_MAX_ROWS rows of x (decode) the
+    bytes are streamed as they are (K.linear_w8); above (prefill) they are
+    dequantised to a bf16 copy that lives for the call and go through the
+    bf16 GEMM. ``swiglu(x)`` is the same for a packed gate|up weight and
+    returns silu(gate) * up."""
+
+    def __init__(self, din, dout, device=None):
+        super().__init__()
+        self.register_buffer("weight8", torch.zeros(
+            dout, din, dtype=torch.float8_e4m3fn, device=device))
+        self.register_buffer("scale", torch.ones(
+            dout, dtype=torch.float32, device=device))
+
+    @classmethod
+    def from_linear(cls, linear):
+        w = linear.weight
+        q = cls(w.size(1), w.size(0), device=w.device)
+        w8, scale = K.moe_quant_weight(w)
+        q.weight8.copy_(w8)
+        q.scale.copy_(scale)
+        return q
+
+    def _streams(self, x):
+        return x.numel() // x.size(-1) <= STREAM_MAX_ROWS
+
+    def _dense(self, x):
+        from ..ops.gemm import tuned_linear
+
+        return tuned_linear(x, K.linear_dequant(self.weight8, self.scale))
+
+    def forward(self, x):
+        if self._streams(x):
+            return K.linear_w8(x, self.weight8, self.scale)
+        return self._dense(x)
+
+    def swiglu(self, x):
+        if self._streams(x):
+            return K.linear_w8(x, self.weight8, self.scale, swiglu=True)
+        return K.swiglu_fused(self._dense(x))
+
+
 class RMSNorm(nn.Module):
     def __init__(self, dim, eps):
         super().__init__()
@@ -161,7 +214,11 @@ class DecoderLayer(nn.Module):
         o = o.transpose(1, 2).reshape(B, S, nq * hd)
         res, y = K.add_rmsnorm(res, self.o_proj(o), self.post_norm.weight,
                                self.post_norm.eps)
-        pending = self.down_proj(K.swiglu_fused(self.gate_up_proj(y)))
+        if isinstance(self.gate_up_proj, Fp8WeightLinear):
+            h = self.gate_up_proj.swiglu(y)
+        else:
+            h = K.swiglu_fused(self.gate_up_proj(y))
+        pending = self.down_proj(h)
         return res, pending
 
     def _rope_qkv_rows(self, qkv, c_rows, s_rows, nq, nkv):
@@ -235,6 +292,41 @@ class LlamaForCausalLM(nn.Module):
         for layer in self.layers:
             layer.o_proj.weight.data.mul_(scale)
             layer.down_proj.weight.data.mul_(scale)
+
+    PROJECTIONS = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj")
+
+    @torch.no_grad()
+    def quantize_weights_(self, lm_head=True):
+        """Weight-only FP8 for serving: replace the four projections of
+        every layer, and ``lm_head`` on request, by Fp8WeightLinear (E4M3
+        bytes and one scale per output row) and free the bf16 parameters.
+        The decode step then streams half the bytes. Every weight must be a
+        multiple of 128 both ways (gate|up: per half); training through
+        quantised projections is not supported. Returns self."""
+        if self.cfg.fp8:
+            raise ValueError(
+                "quantize_weights_ is weight-only FP8 for serving; cfg.fp8 "
+                "is the training format (ops/fp8.py) and does not combine "
+                "with it")
+        todo = [("layers.%d.%s" % (i, n), layer, n)
+                for i, layer in enumerate(self.layers)
+                for n in self.PROJECTIONS]
+        if lm_head:
+            todo.append(("lm_head", self, "lm_head"))
+        todo = [t for t in todo
+                if not isinstance(getattr(t[1], t[2]), Fp8WeightLinear)]
+        for name, owner, attr in todo:
+            dout, din = getattr(owner, attr).weight.shape
+            halves = 2 if attr == "gate_up_proj" else 1
+            if din % 128 or dout % (128 * halves):
+                raise ValueError(
+                    "quantize_weights_: %s is [%d, %d]; the FP8 stream "
+                    "kernel needs multiples of 128 (per half of gate|up)"
+                    % (name, dout, din))
+        for _, owner, attr in todo:
+            setattr(owner, attr,
+                    Fp8WeightLinear.from_linear(getattr(owner, attr)))
+        return self
 
     def forward(self, tokens, targets=None, cache=None):
         """tokens [B, S] int64 (the LOCAL shard when cp_group is set);

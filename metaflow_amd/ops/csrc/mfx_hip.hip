@@ -19,6 +19,7 @@
 #include "sampling.hip"
 #include "moe.hip"
 #include "moe_prefill.hip"
+#include "linear_fp8.hip"
 #include "debug_kernels.hip"
 
 namespace {
@@ -950,10 +951,7 @@ std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t k,
   return {r.expert, r.weight, r.order, r.offset, r.slot};
 }
 
-// Split-K of the down projection, from shapes alone: enough blocks to
-// cover the chip twice when only min(E, T*k) experts can be active.
-int moe_down_splits(long long E, long long entries, long long hidden,
-                    long long inter) {
+int cu_count() {
   static int cus = 0;
   if (cus == 0) {
     int dev = 0;
@@ -963,6 +961,14 @@ int moe_down_splits(long long E, long long entries, long long hidden,
                     hipSuccess && cus > 0,
                 "cannot read the CU count");
   }
+  return cus;
+}
+
+// Split-K of the down projection, from shapes alone: enough blocks to
+// cover the chip twice when only min(E, T*k) experts can be active.
+int moe_down_splits(long long E, long long entries, long long hidden,
+                    long long inter) {
+  const int cus = cu_count();
   const long long active = std::min(E, entries) * (hidden / MOE_ROWS);
   const long long want = (2ll * cus + active - 1) / active;
   return (int)std::max<long long>(
@@ -1053,6 +1059,131 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor logits,
       (int)entries, (int)hidden, (int)inter);
   HIP_CHECK_KERNEL();
   moe_combine(y, r, out, T, k, splits, hidden);
+  return out;
+}
+
+// ------------------------------------------- dense W8A16 (linear_fp8.hip)
+// Split-K of a dense stream GEMM with N / 128 row blocks, from shapes
+// alone: enough blocks to cover the chip twice, but at least four chunks
+// per split and at most 16 splits (measured on o_proj and down_proj,
+// docs/KERNELS.md "FP8 dense weights": o_proj is fastest at 8 splits of 4
+// chunks, down_proj at 16 of 7).
+int lin_splits(long long blocks, long long K) {
+  const long long want = (2ll * cu_count() + blocks - 1) / blocks;
+  return (int)std::max<long long>(
+      1, std::min<long long>({want, K / (4 * MOE_KC), 16ll}));
+}
+
+template <typename W>
+using lin_kernel_t = void (*)(const short*, const W*, const float*, short*,
+                              float*, int, int, int);
+
+template <typename W>
+void lin_launch(const lin_kernel_t<W> (&kern)[2][2], const torch::Tensor& x,
+                const torch::Tensor& w, const float* scale,
+                torch::Tensor& out, float* part, bool swiglu, int splits,
+                int M, int K, int N) {
+  const lin_kernel_t<W> k = kern[M > 32 ? 1 : 0][swiglu ? 1 : 0];
+  k<<<dim3(N / MOE_ROWS, splits), MOE_BLOCK, 0, cur_stream()>>>(
+      bf(x), reinterpret_cast<const W*>(w.data_ptr()), scale, bfm(out), part,
+      M, K, N);
+  HIP_CHECK_KERNEL();
+}
+
+// x [M, K] bf16; w [NW, K] bf16, or uint8 E4M3 bytes with scale fp32 [NW];
+// NW = N, or 2 N with swiglu (gate rows, then up rows) -> [M, N] bf16.
+// splits <= 0 picks the split of K from the shapes. NB = 1 up to 32 rows,
+// 2 above. Nothing is read on the host.
+torch::Tensor linear_w8(torch::Tensor x, torch::Tensor w,
+                        c10::optional<torch::Tensor> scale, bool swiglu,
+                        int64_t splits) {
+  check_bf16(x, "x");
+  const bool e4m3 = w.scalar_type() == torch::kByte;
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() &&
+              (e4m3 || w.scalar_type() == torch::kBFloat16),
+              "w must be a contiguous [out, in] GPU tensor of bf16, or of "
+              "E4M3 bytes viewed as uint8");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == w.size(1),
+              "x must be [M, K] for w [out, K]");
+  const long long M = x.size(0), K = x.size(1), NW = w.size(0);
+  const long long N = swiglu ? NW / 2 : NW;
+  TORCH_CHECK(K > 0 && K % 128 == 0,
+              "linear_w8 needs K (in features) to be a multiple of 128, "
+              "got ", K);
+  TORCH_CHECK(N > 0 && N % 128 == 0 && (swiglu ? 2 * N : N) == NW,
+              "linear_w8 needs ", swiglu ? "inter (half of w's rows)"
+                                         : "N (out features)",
+              " to be a multiple of 128, got ", swiglu ? NW / 2.0 : N);
+  TORCH_CHECK(M >= 1 && M * NW < (1ll << 31), "linear_w8 needs 1 <= M and "
+              "M * out < 2^31, got M = ", M);
+  TORCH_CHECK(e4m3 == scale.has_value(),
+              "scale goes with E4M3 weights, and only with them");
+  const float* sp = nullptr;
+  if (e4m3) {
+    const torch::Tensor& s = *scale;
+    TORCH_CHECK(s.is_cuda() && s.scalar_type() == torch::kFloat32 &&
+                s.dim() == 1 && s.size(0) == NW && s.is_contiguous() &&
+                (reinterpret_cast<uintptr_t>(s.data_ptr()) & 15) == 0,
+                "scale must be a contiguous 16-byte-aligned fp32 [out] on "
+                "GPU");
+    sp = s.data_ptr<float>();
+  }
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(x.data_ptr()) |
+                reinterpret_cast<uintptr_t>(w.data_ptr())) & 15) == 0,
+              "x and w must be 16-byte aligned");
+  if (splits <= 0) splits = lin_splits(N / MOE_ROWS, K);
+  TORCH_CHECK(splits <= K / MOE_KC && splits <= 64,
+              "splits must be at most K / 128 and 64");
+  auto out = torch::empty({M, N}, x.options());
+  torch::Tensor part;
+  float* pp = nullptr;
+  if (splits > 1) {
+    part = torch::empty({splits, M, NW}, x.options().dtype(torch::kFloat32));
+    pp = part.data_ptr<float>();
+  }
+  if (e4m3) {
+    static const lin_kernel_t<moe_e4m3> kern[2][2] = {
+        {lin_stream_fp8_nb1_kernel, lin_stream_fp8_nb1_swiglu_kernel},
+        {lin_stream_fp8_nb2_kernel, lin_stream_fp8_nb2_swiglu_kernel}};
+    lin_launch<moe_e4m3>(kern, x, w, sp, out, pp, swiglu, (int)splits,
+                         (int)M, (int)K, (int)N);
+  } else {
+    static const lin_kernel_t<short> kern[2][2] = {
+        {lin_stream_bf16_nb1_kernel, lin_stream_bf16_nb1_swiglu_kernel},
+        {lin_stream_bf16_nb2_kernel, lin_stream_bf16_nb2_swiglu_kernel}};
+    lin_launch<short>(kern, x, w, sp, out, pp, swiglu, (int)splits, (int)M,
+                      (int)K, (int)N);
+  }
+  if (splits > 1) {
+    lin_reduce_kernel<<<(unsigned)((M * (N / 4) + 255) / 256), 256, 0,
+                        cur_stream()>>>(pp, bfm(out), (int)splits, (int)M,
+                                        (int)N, swiglu ? 1 : 0);
+    HIP_CHECK_KERNEL();
+  }
+  return out;
+}
+
+// w8 [rows, K] E4M3 bytes (uint8 view), scale fp32 [rows] -> bf16 [rows, K]
+torch::Tensor linear_dequant(torch::Tensor w8, torch::Tensor scale) {
+  TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == torch::kByte &&
+              w8.dim() == 2 && w8.is_contiguous(),
+              "w8 must be contiguous [out, in] E4M3 bytes viewed as uint8 "
+              "on GPU");
+  const long long rows = w8.size(0), K = w8.size(1);
+  TORCH_CHECK(K > 0 && K % 16 == 0 && rows > 0,
+              "linear_dequant needs K (in features) to be a multiple of 16, "
+              "got ", K);
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat32 &&
+              scale.dim() == 1 && scale.size(0) == rows &&
+              scale.is_contiguous(),
+              "scale must be a contiguous fp32 [out] on GPU");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(w8.data_ptr()) & 15) == 0,
+              "w8 must be 16-byte aligned");
+  auto out = torch::empty({rows, K}, w8.options().dtype(torch::kBFloat16));
+  lin_dequant_kernel<<<grid_for(rows * (K / 16)), 256, 0, cur_stream()>>>(
+      w8.data_ptr<uint8_t>(), scale.data_ptr<float>(), bfm(out), rows,
+      (int)K);
+  HIP_CHECK_KERNEL();
   return out;
 }
 
@@ -1168,6 +1299,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "weight address table, top_k, inter, down splits (<= 0 = from "
         "shapes), tiled (the prefill kernels), e4m3 (E4M3 weights, table "
         "[6,E] with the row-scale addresses) -> [T,hidden]");
+  m.def("linear_w8", &linear_w8,
+        "skinny stream GEMM: x [M,K] bf16, w [out,K] bf16 or E4M3 bytes "
+        "(uint8) with fp32 row scales, swiglu (w = gate|up), splits (<= 0 "
+        "= from shapes) -> [M,N] bf16");
+  m.def("linear_dequant", &linear_dequant,
+        "E4M3 bytes (uint8) [out,K] * fp32 row scales -> bf16 [out,K]");
   m.def("dbg_mfma32", &dbg_mfma32, "mfma 32x32x16 layout probe");
   m.def("dbg_attn_layout", &dbg_attn_layout,
         "attention panel / transposed-read / col_to_afrags layout probe");

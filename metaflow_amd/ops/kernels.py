@@ -996,12 +996,12 @@ def _moe_check_route(T, E, top_k):
                          % (MOE_MAX_ENTRIES, T))
 
 
-def _moe_no_grad(*tensors):
+def _moe_no_grad(*tensors, what="the fused MoE path"):
     if torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in tensors):
         raise RuntimeError(
-            "the fused MoE path is inference-only: call it under "
-            "torch.no_grad() or with inputs that do not require grad")
+            "%s is inference-only: call it under torch.no_grad() or with "
+            "inputs that do not require grad" % what)
 
 
 def moe_route_ref(logits, top_k):
@@ -1225,6 +1225,88 @@ def moe_ffn(x, logits, w_gate, w_up=None, w_down=None, top_k=2,
     return hip_ext().moe_ffn(x.contiguous(), logits.float().contiguous(),
                              table.tab, top_k, table.inter,
                              down_splits or 0, path == "tiled", table.fp8)
+
+
+# ======================= dense weight-only FP8 =============================
+def _linear_w8_shapes(x, w, scale, swiglu):
+    fp8 = w.dtype == torch.float8_e4m3fn
+    if w.dim() != 2 or not (fp8 or w.dtype == torch.bfloat16):
+        raise ValueError("linear_w8: w must be [out, in] float8_e4m3fn (with "
+                         "scale) or bf16")
+    if fp8 != (scale is not None):
+        raise ValueError("linear_w8: scale goes with float8_e4m3fn weights, "
+                         "and only with them")
+    rows, kdim = w.shape
+    if fp8 and tuple(scale.shape) != (rows,):
+        raise ValueError("linear_w8: scale must be fp32 [%d]" % rows)
+    if x.size(-1) != kdim:
+        raise ValueError("linear_w8: x must be [..., %d]" % kdim)
+    if kdim % 128:
+        raise ValueError("linear_w8 needs K (in features) to be a multiple "
+                         "of 128, got %d" % kdim)
+    if swiglu and rows % 256:
+        raise ValueError("linear_w8 needs inter (half of w's rows) to be a "
+                         "multiple of 128, got %s" % (rows / 2))
+    if rows % 128:
+        raise ValueError("linear_w8 needs N (out features) to be a multiple "
+                         "of 128, got %d" % rows)
+    return fp8, rows // 2 if swiglu else rows
+
+
+def linear_w8_ref(x, w, scale, swiglu=False, dtype=torch.float64):
+    """Reference of linear_w8 in ``dtype`` with no intermediate rounding,
+    on the exactly dequantised weights (moe_dequant_ref; a bf16 ``w`` with
+    ``scale=None`` is taken as it is): x @ w.T, and with ``swiglu`` silu of
+    the first half of the columns times the second. Returns ``dtype``."""
+    wd = w.to(dtype) if scale is None else moe_dequant_ref(w, scale, dtype)
+    y = x.to(dtype) @ wd.t()
+    if swiglu:
+        g, u = y.chunk(2, dim=-1)
+        y = torch.nn.functional.silu(g) * u
+    return y
+
+
+def linear_w8(x, w, scale=None, swiglu=False, splits=None):
+    """Weight-only FP8 linear for a few rows: x [..., K] bf16 times w^T ->
+    [..., N] bf16, fp32 accumulation, one rounding.
+
+    w: float8_e4m3fn [N, K] with ``scale`` fp32 [N], one per output row
+    (moe_quant_weight), or bf16 [N, K] with ``scale=None``: the same kernel
+    over two-byte weights, a control for benchmarks and tests. With
+    ``swiglu`` w is the packed gate|up weight [2 inter, K] and the result is
+    silu(x gate^T) * (x up^T), [..., inter], still one rounding. K and N
+    (inter) must be multiples of 128.
+
+    GPU -> linear_fp8.hip: every weight byte is read once per 64 rows of x
+    and goes straight into MFMA registers, so the call is for decode-sized
+    M; it is correct for any M. ``splits``: split of K over blocks, None
+    picks it from the shapes and the CU count; above one, fp32 partials are
+    summed in order by a second launch (no atomics). Nothing is read on the
+    host: deterministic and hipGraph-capturable. CPU -> linear_w8_ref in
+    fp32. Inference-only."""
+    fp8, n_out = _linear_w8_shapes(x, w, scale, swiglu)
+    _moe_no_grad(x, w, what="linear_w8")
+    lead = x.shape[:-1]
+    if not x.is_cuda:
+        return linear_w8_ref(x, w, scale, swiglu, torch.float32).to(x.dtype)
+    if splits is not None and not 1 <= splits <= min(w.size(1) // 128, 64):
+        raise ValueError("splits must be in [1, min(K / 128, 64)]")
+    x2 = x.reshape(-1, x.size(-1)).contiguous()
+    if x2.size(0) == 0:
+        return x.new_empty(lead + (n_out,))
+    y = hip_ext().linear_w8(x2, w.view(torch.uint8) if fp8 else w, scale,
+                            bool(swiglu), splits or 0)
+    return y.view(lead + (n_out,))
+
+
+def linear_dequant(w8, scale):
+    """bf16 [N, K] = e4m3(w8) * scale[:, None], computed in fp32 and rounded
+    once: GPU -> one pass of linear_fp8.hip, CPU -> moe_dequant_ref. The
+    large-M fallback of the weight-only FP8 linears feeds it to a bf16
+    GEMM."""
+    if not w8.is_cuda:
+        return moe_dequant_ref(w8, scale, torch.bfloat16)
+    return hip_ext().linear_dequant(w8.view(torch.uint8), scale)
 
 
 # ================================ adam =====================================
